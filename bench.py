@@ -14,7 +14,14 @@ weights; inputs are resident in HBM before the timed region.  Weak scaling: per-
 `--gpus N` without a torchrun environment re-executes itself under `python -m torch.distributed.run` with N
 ranks (reference behaviour: common/launch_utils.py:26-42); a WORLD_SIZE that disagrees with --gpus is an error.
 
-The single JSON line (< 4 KB, last line of stdout) also carries
+A plain run sets up, runs the W warm-up and K timed steps and prints one JSON line (< 4 KB, last line of stdout) with
+`metric`, `value` (pairs/s), `unit`, `higher_is_better`, `dtype` and `ms_per_step` (one timed step).
+`--dump-outputs DIR` writes what the last timed step handed its caller as DIR/<name>.npy (see dump_outputs()); the
+inputs and the initial weights are seeded, so two builds run with the same arguments can be compared file by file.
+
+`--full` (off by default) adds every figure that takes passes of its own after the timed region: the companion values
+(full-length text, no pad objects, both at once, device sampler, single-product SA mode), the per-kernel timing pass,
+the torch.profiler pass, the unfused ball_query + group timing and the CPU baseline.  The JSON line then also carries
   roofline      the kernel family with the largest time per step among ALL kernels of the step (native launches by
                 HIP events, everything else by a torch.profiler pass): ALGORITHMIC flops (or bytes) / measured
                 duration vs the dense MFMA peak of its dtype (or 8 TB/s), + PMC HBM traffic of its largest shape
@@ -119,6 +126,41 @@ def write_detail(detail: dict, path=None) -> None:
         print(f"[bench] per-kernel detail written to {path}", file=sys.stderr)
     except OSError as e:
         print(f"[bench] could not write {path}: {e}", file=sys.stderr)
+
+
+DUMP_PARAM_SAMPLE = 1 << 20     # elements of the seeded sample of the updated parameters (4 MB as float32)
+
+
+def dump_outputs(out_dir: str, model, loss, losses) -> None:
+    """What the last timed step handed its caller, as float32 / float64 .npy files under `out_dir` (~4 MB in all):
+      total_loss.npy      the step's total loss (float64, shape (1,))
+      loss_<name>.npy     every loss term of the `losses` dict (float64)
+      param_norms.npy     L2 norm of every trainable parameter after the step's AdamW update, named_parameters order (float64)
+      param_sample.npy    the same parameters flattened and concatenated in that order, at DUMP_PARAM_SAMPLE positions
+                          drawn with a fixed seed, ascending (float32; the full set is several hundred MB)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    files = {"total_loss": np.asarray([float(loss)], dtype=np.float64)}
+    for name, v in sorted(losses.items()):
+        files["loss_" + "".join(c if c.isalnum() else "_" for c in name)] = v.detach().double().reshape(-1).cpu().numpy()
+    params = [p.detach() for _, p in model.named_parameters() if p.requires_grad]
+    files["param_norms"] = torch.stack([p.double().norm() for p in params]).cpu().numpy()
+    sizes = torch.tensor([p.numel() for p in params], dtype=torch.int64)
+    total = int(sizes.sum())
+    g = torch.Generator().manual_seed(20240607)
+    pos = torch.randint(total, (min(DUMP_PARAM_SAMPLE, total),), generator=g, dtype=torch.int64).sort().values
+    ends = sizes.cumsum(0)
+    owner = torch.searchsorted(ends, pos, right=True)           # which parameter each position falls in
+    local = pos - (ends - sizes)[owner]
+    sample = torch.empty(pos.numel(), dtype=torch.float32)
+    for i in owner.unique().tolist():
+        sel = (owner == i).nonzero().squeeze(1)
+        p = params[i].reshape(-1)
+        sample[sel] = p[local[sel].to(p.device)].float().cpu()
+    files["param_sample"] = sample.numpy()
+    for name, arr in files.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), arr)
+    print(f"[bench] {len(files)} output arrays written to {out_dir}", file=sys.stderr)
 
 
 # workload presets: BASELINE.json configs[1] (default), configs[3] and configs[4]
@@ -456,6 +498,11 @@ def main() -> None:
                          "its maximum length (no padded rows to skip: what `value_full_length_text` reports beside `value`)")
     ap.add_argument("--no-extras", action="store_true",
                     help="skip the reporting-only passes after the timed region (profiler, unfused point-op timing)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: companion values, per-kernel roofline, "
+                         "profiler pass, unfused ball_query + group, CPU baseline, detail file (off: timed steps only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
 
     if args.cpu_baseline_worker:
@@ -624,17 +671,21 @@ def main() -> None:
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss, _ = step.step(dict(batch))
+        loss, losses = step.step(dict(batch))
     barrier()
     dt = time.perf_counter() - t0
     exposed_ms = step.exposed_allreduce_ms() if step.graph_dp else None     # of the last timed step
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step.model, loss, losses)
+    # everything below up to the JSON line is --full only (a plain run times the K steps and reports them)
+    extras = args.full and not args.no_extras
     # The same step with EVERY sentence at 50 and every caption at 300 tokens (no padded text rows at all): what the
     # variable-length text path gains depends on the caption-length distribution of the synthetic batch (U{30..300}),
     # so the fully-populated figure is measured beside `value`, same process, same graphs (the row counts live on the
     # device), W warm-up + K timed steps.
     dt_full = None
     full = None
-    if preset["scene_cap"] and not args.no_extras and args.text_lengths != "full":
+    if preset["scene_cap"] and extras and args.text_lengths != "full":
         # (`batch` may alias the graph's static input buffers: keep the measured texts aside and put them back after)
         saved_text = {k: batch[k].clone() for k in ("txt_ids", "txt_masks", "scene_txt_ids", "scene_txt_masks")}
         full = {**batch, **full_length_texts(batch, 4242 + rank)}
@@ -656,7 +707,7 @@ def main() -> None:
     dt_nopad = None
     dt_cons = None
     pad_frac = None
-    if "obj_fts" in batch and "obj_masks" in batch and not args.no_extras and not args.all_object_slots:
+    if "obj_fts" in batch and "obj_masks" in batch and extras and not args.all_object_slots:
         pads = batch["obj_masks"].logical_not()
         pad_frac = float(pads.float().mean().item())
         saved_obj = batch["obj_fts"].clone()
@@ -692,7 +743,7 @@ def main() -> None:
     # resident in HBM (packed once, untimed), every step draws + normalises the 80 x 1024 points of every scene straight
     # into the graph's static input buffers (gps_obj_processing_post) and then replays the step.
     dt_samp = None
-    if args.config == "pretrain" and not args.no_extras and use_graph and step.static_inputs() is not None:
+    if args.config == "pretrain" and extras and use_graph and step.static_inputs() is not None:
         import numpy as np
         from sceneverse_amd.data import gpu_objects as G
         rng = np.random.default_rng(7 + rank)
@@ -723,7 +774,7 @@ def main() -> None:
     # within 5.8e-3 max of the fp32 path): the product count is baked into the captured launches, so this is a second engine
     # (same configuration and seed), W warm-up + K timed steps.
     dt_sa16 = None
-    if (args.config == "pretrain" and not args.no_extras and not args.sa_bf16 and not args.fp32 and world == 1 and step.graph
+    if (args.config == "pretrain" and extras and not args.sa_bf16 and not args.fp32 and world == 1 and step.graph
             and not args.all_object_slots):
         from sceneverse_amd.pointnet2 import pointnet2_modules as _sam
         _sam.set_sa_precision("bf16")
@@ -753,16 +804,18 @@ def main() -> None:
     # the host's launch path inside the number being reported.
     saved = (step.graph, step.graph_dp) if use_graph else None
     saved_overlap = step.wgrad_overlap
-    step.wgrad_overlap = False      # per-kernel durations are taken with every launch alone on the GPU (one stream)
-    if use_graph:
-        step.graph = step.graph_dp = False
-        step.step(dict(batch))
-    hip_ext.profile_start()
-    for _ in range(3):
-        step.step(dict(batch))
-    kern = hip_ext.profile_stop()
-    for k in kern.values():
-        k["launches"] = k["launches"] * args.steps / 3.0
+    kern = {}
+    if args.full:
+        step.wgrad_overlap = False      # per-kernel durations are taken with every launch alone on the GPU (one stream)
+        if use_graph:
+            step.graph = step.graph_dp = False
+            step.step(dict(batch))
+        hip_ext.profile_start()
+        for _ in range(3):
+            step.step(dict(batch))
+        kern = hip_ext.profile_stop()
+        for k in kern.values():
+            k["launches"] = k["launches"] * args.steps / 3.0
     t = torch.tensor([dt, dt_full or 0.0, dt_samp or 0.0, dt_nopad or 0.0], device=dev, dtype=torch.float64)
     if world > 1:
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
@@ -776,11 +829,15 @@ def main() -> None:
         # one evaluation pass through the grounding metrics (evaluator/scanrefer_eval.py:14-87); synthetic boxes:
         # the annotated target is the only object above both IoU thresholds
         from sceneverse_amd.engine import scanrefer_accuracy
+        if use_graph and not args.full:
+            # no eager step since the replays (they update the masters behind Python's back): rebuild the bf16 shadows
+            from sceneverse_amd.modules.layers import gemm as _gemm
+            _gemm.invalidate_shadows()
         out, _, _ = step.evaluate(dict(batch))
         onehot = torch.zeros_like(out["og3d_logits"], dtype=torch.long)
         onehot.scatter_(1, batch["tgt_object_id"], 1)
         eval_metrics = scanrefer_accuracy(out["og3d_logits"].float(), onehot, onehot)
-    if rank == 0 and not args.no_extras:
+    if rank == 0 and extras:
         if world == 1:
             step_kernels = profile_step_kernels(step, batch)        # eager steps (graph flags are off here)
         if args.config == "pretrain":
@@ -1032,7 +1089,9 @@ def main() -> None:
             "roofline": roofline,
             "headline": headline,
         }
-        if world == 1 and not args.no_cpu_baseline and args.config == "pretrain":
+        if not args.full:       # no per-kernel pass ran: the line carries the timed figures only
+            del result["roofline"], result["headline"]
+        if args.full and world == 1 and not args.no_cpu_baseline and args.config == "pretrain":
             result["cpu_baseline"] = cpu_baseline(args.cpu_batch, args.cpu_steps, args.n_obj, args.n_pts)
             # the CPU leg runs HF BERT on every row of the padded (B, L) batch: its like-for-like GPU figure is
             # value_full_length_text (no padded rows to skip), not `value`
@@ -1045,7 +1104,8 @@ def main() -> None:
                                 kernel_timing="HIP events around each native launch in three eager steps right after the timed region")
         detail.update({"headline": headline_full, "kernel_families": kernel_families, "kernels": kernels,
                        "step_kernels": step_kernels[:25]})
-        write_detail(detail, args.detail)
+        if args.full:
+            write_detail(detail, args.detail)
         print(final_line(result), flush=True)
     if world > 1:
         torch.distributed.barrier()

@@ -213,6 +213,40 @@ def test_bench_rank_resolution_rules():
     assert cmd[cmd.index("--master-addr") + 1] == "127.0.0.1" and cmd[-4:] == ["--gpus", "4", "--steps", "3"]
 
 
+def test_bench_dump_outputs_writes_the_step_results(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: losses as float64, parameter norms, and a seeded, ascending sample of the flattened
+    trainable parameters (float32) that is the same on every call."""
+    import os
+    import sys
+
+    import numpy as np
+    argv, sys.argv = sys.argv, ["bench.py"]
+    try:
+        import bench
+    finally:
+        sys.argv = argv
+    monkeypatch.setattr(bench, "DUMP_PARAM_SAMPLE", 500)
+    torch.manual_seed(0)
+    model = torch.nn.Sequential(torch.nn.Linear(30, 40), torch.nn.Linear(40, 7))
+    model[1].bias.requires_grad_(False)
+    losses = {"lm_cls_loss": torch.tensor(0.25), "Text/Obj": torch.tensor(1.0)}
+    bench.dump_outputs(str(tmp_path / "a"), model, torch.tensor(1.25), losses)
+    bench.dump_outputs(str(tmp_path / "b"), model, torch.tensor(1.25), losses)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["loss_Text_Obj.npy", "loss_lm_cls_loss.npy", "param_norms.npy", "param_sample.npy", "total_loss.npy"]
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b)
+    assert np.load(tmp_path / "a" / "total_loss.npy").tolist() == [1.25]
+    trainable = [p.detach() for p in model.parameters() if p.requires_grad]
+    norms = np.load(tmp_path / "a" / "param_norms.npy")
+    assert norms.dtype == np.float64 and np.allclose(norms, [float(p.double().norm()) for p in trainable])
+    flat = torch.cat([p.reshape(-1) for p in trainable])
+    sample = np.load(tmp_path / "a" / "param_sample.npy")
+    assert sample.dtype == np.float32 and sample.shape == (500,)
+    assert np.isin(sample, flat.numpy()).all()
+
+
 def test_graph_step_rejects_batches_that_do_not_match_the_capture():
     """GPSTrainStep._fill_static: same keys, shapes and dtypes as the captured batch, or a clear error."""
     import types

@@ -393,7 +393,7 @@ def test_bench_n2_code_path_on_one_gpu(extra):
     env = dict(os.environ, GPS_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"),
-           "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "8"] + extra
+           "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "8", "--full"] + extra
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -428,6 +428,37 @@ def test_bench_self_spawns_its_ranks():
     assert len(lines) == 1, r.stdout[-2000:]
     out = json.loads(lines[0])
     assert out["n_gpus"] == 2 and out["config"]["global_batch"] == 16
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_one(tmp_path):
+    """`python bench.py --gpus 1` without --full: the timed steps and the line only (no companion figures, roofline or
+    CPU baseline); --dump-outputs writes the last timed step's losses and updated parameters as float .npy files."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dump = tmp_path / "out"
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "8",
+           "--dump-outputs", str(dump)]
+    r = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["higher_is_better"] is True
+    assert out["unit"] == "pairs/s" and out["dtype"] == "bf16" and out["metric"].startswith("GPS pre-train")
+    assert abs(out["value"] - 8 / (out["ms_per_step"] * 1e-3)) < 0.02 * out["value"]
+    assert not {"roofline", "headline", "cpu_baseline", "value_full_length_text", "value_sa_bf16"} & set(out)
+    names = sorted(os.listdir(dump))
+    assert {"total_loss.npy", "param_norms.npy", "param_sample.npy"} <= set(names)
+    assert any(n.startswith("loss_") for n in names)
+    for n in names:
+        a = np.load(dump / n)
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), n
+    assert abs(float(np.load(dump / "total_loss.npy")[0]) - out["config"]["final_loss"]) < 1e-3
 
 
 def _bench_slice(n_scenes=2):

@@ -1,7 +1,10 @@
 """Pins the oracle: the fp32 PyTorch restatement (oracle/gps_torch_reference.py, on top of the C
 point-op oracle) must reproduce what the REFERENCE's own Python produced on the same inputs and
 weights (tests/golden/gps_reference_cpu.pt, written by tests/golden/make_golden.py)."""
+import os
+
 import torch
+from conftest import GOLDEN_DIR
 
 from oracle import gps_torch_reference as R
 from oracle.param_fill import fill_params
@@ -29,9 +32,33 @@ def test_pointnetpp_adversarial_objects(golden_cpu):
     torch.testing.assert_close(out, fx["pointnetpp_adv_out"], **TOL)
 
 
-def test_pairwise_locs_bit_exact(golden_cpu):
+def test_pairwise_locs_bit_exact(golden_cpu, monkeypatch):
+    """Bit for bit.  torch's CPU sqrt goes through MKL's vector math, whose last bit depends on the host CPU (an AMD EPYC
+    host returns 1 - 2 ulp different roots for some of these inputs than the host the fixture was written on).  Where
+    this host's roots differ from the recorded ones (tests/golden/pairwise_sqrt_ref_host.pt), the same oracle code runs
+    with torch.sqrt answering every root from that table: all other operations must still reproduce the reference."""
     fx = golden_cpu
-    assert torch.equal(R.calc_pairwise_locs(fx["batch"]["obj_locs"][:, :, :3]), fx["pairwise_locs"])
+    table = torch.load(os.path.join(GOLDEN_DIR, "pairwise_sqrt_ref_host.pt"))
+    xs, roots = table["x"], table["sqrt"]
+    host = torch.sqrt(xs)
+    if not torch.equal(host, roots):
+        assert (host.view(torch.int32) - roots.view(torch.int32)).abs().max().item() <= 2     # a rounding difference only
+        real_sqrt = torch.sqrt
+
+        def recorded_sqrt(t):
+            flat = t.reshape(-1)
+            pos = torch.searchsorted(xs, flat).clamp(max=xs.numel() - 1)
+            assert torch.equal(xs[pos], flat), "a square root of an input the table does not hold"
+            return roots[pos].reshape(t.shape)
+
+        monkeypatch.setattr(torch, "sqrt", recorded_sqrt)
+        try:
+            got = R.calc_pairwise_locs(fx["batch"]["obj_locs"][:, :, :3])
+        finally:
+            monkeypatch.setattr(torch, "sqrt", real_sqrt)
+    else:
+        got = R.calc_pairwise_locs(fx["batch"]["obj_locs"][:, :, :3])
+    assert torch.equal(got, fx["pairwise_locs"])
 
 
 def test_spatial_and_joint_layers(golden_cpu):

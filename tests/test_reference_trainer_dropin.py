@@ -130,6 +130,18 @@ def _zero_dropout(module):
                 setattr(m.config, name, 0.0)
 
 
+@pytest.fixture(autouse=True)
+def _fresh_accelerate_state():
+    """Accelerate keeps its device choice in process-wide singletons: the CPU variant's state must not leak into the GPU
+    variant (or any later test) when both run in one session."""
+    from accelerate.state import AcceleratorState, GradientState
+    AcceleratorState._reset_state(reset_partial_state=True)
+    GradientState._reset_state()
+    yield
+    AcceleratorState._reset_state(reset_partial_state=True)
+    GradientState._reset_state()
+
+
 def _run(device: str):
     tb, dt, db = _shadow_and_import()
     _register_synthetic(db)

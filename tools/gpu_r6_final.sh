@@ -14,11 +14,11 @@ ts pytest; timeout 1500 python -m pytest tests -m gpu -q -s > $OUT/pytest_gpu_fu
 grep -E "^(FAILED|ERROR)|passed|failed|pytest exit" $OUT/pytest_gpu_full.log | head -20
 grep "bf16-vs-fp32" $OUT/pytest_gpu_full.log > $OUT/bounds_default.log; wc -l $OUT/bounds_default.log
 grep -E "^(FAILED|ERROR)|passed|failed|skipped|pytest exit|warnings summary" $OUT/pytest_gpu_full.log > $OUT/pytest_gpu.log
-ts bench; timeout 900 python bench.py --steps 20 --warmup 5 --detail $OUT/bench_detail.json > $OUT/bench.json 2> $OUT/bench.err; echo "bench exit $?"
+ts bench; timeout 900 python bench.py --full --steps 20 --warmup 5 --detail $OUT/bench_detail.json > $OUT/bench.json 2> $OUT/bench.err; echo "bench exit $?"
 tail -c 1500 $OUT/bench.json; tail -3 $OUT/bench.err
 ts rocprof
 rm -rf /tmp/prof && mkdir -p /tmp/prof
-(cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/prof -o bench --output-format csv -- python $REPO/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-extras --detail $OUT/bench_prof_detail.json > $OUT/prof_bench.log 2>&1; echo "rocprof exit $?")
+(cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/prof -o bench --output-format csv -- python $REPO/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-extras --detail $OUT/bench_prof_detail.json > $OUT/prof_bench.log 2>&1; echo "rocprof exit $?")
 find /tmp/prof -name '*kernel_stats*.csv' -exec cp {} $OUT/bench_kernel_stats.csv \;
 find /tmp/prof -name '*kernel_trace*.csv' -exec cp {} /tmp/bench_kernel_trace.csv \;
 python tools/step_from_trace.py /tmp/bench_kernel_trace.csv --json $OUT/step_from_trace.json > $OUT/step_from_trace.txt 2>&1; head -22 $OUT/step_from_trace.txt

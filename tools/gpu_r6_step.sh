@@ -7,7 +7,7 @@ REPO=$PWD
 OUT=$REPO/gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-timeout 900 python bench.py --steps 20 --warmup 5 --detail $OUT/bench_detail.json ${BENCH_FLAGS:-} > $OUT/bench.json 2> $OUT/bench.err; echo "bench exit $?"
+timeout 900 python bench.py --full --steps 20 --warmup 5 --detail $OUT/bench_detail.json ${BENCH_FLAGS:-} > $OUT/bench.json 2> $OUT/bench.err; echo "bench exit $?"
 python - <<PY
 import json
 d=json.loads(open("$OUT/bench.json").read().strip().splitlines()[-1])

@@ -16,7 +16,7 @@ if [[ $WHAT == all || $WHAT == *test* ]]; then
   grep -E "^(FAILED|ERROR)|AssertionError|passed|failed|exit" $OUT/pytest_gpu.log | head -30
 fi
 if [[ $WHAT == all || $WHAT == *bench* ]]; then
-  ts bench; timeout 900 python bench.py --steps 10 --warmup 3 > $OUT/bench.json 2> $OUT/bench.err; echo "bench exit $?"
+  ts bench; timeout 900 python bench.py --full --steps 10 --warmup 3 > $OUT/bench.json 2> $OUT/bench.err; echo "bench exit $?"
   tail -c 4000 $OUT/bench.json; tail -5 $OUT/bench.err
 fi
 if [[ $WHAT == all || $WHAT == *kbench* ]]; then
@@ -25,7 +25,7 @@ fi
 if [[ $WHAT == all || $WHAT == *prof* ]]; then
   ts rocprof
   rm -rf /tmp/prof && mkdir -p /tmp/prof
-  (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/prof -o bench --output-format csv -- python $REPO/bench.py --steps 5 --warmup 2 --no-cpu-baseline > $OUT/prof_bench.log 2>&1; echo "rocprof exit $?")
+  (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/prof -o bench --output-format csv -- python $REPO/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > $OUT/prof_bench.log 2>&1; echo "rocprof exit $?")
   mkdir -p $OUT/prof
   find /tmp/prof -name '*stats*.csv' -exec cp {} $OUT/prof/ \;
   ls -la /tmp/prof/* | head; du -sh /tmp/prof

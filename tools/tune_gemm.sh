@@ -9,6 +9,6 @@ export PYTORCH_TUNABLEOP_FILENAME=$PWD/$OUT/tunableop_gfx950.csv
 export PYTORCH_TUNABLEOP_MAX_TUNING_DURATION_MS=${TUNE_MS:-15} PYTORCH_TUNABLEOP_MAX_WARMUP_DURATION_MS=2
 export GPS_NO_TUNABLEOP_FILE=1
 date
-timeout ${TUNE_TIMEOUT:-420} python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-graph > $OUT/bench_tuning.json 2> $OUT/bench_tuning.err
+timeout ${TUNE_TIMEOUT:-420} python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-graph > $OUT/bench_tuning.json 2> $OUT/bench_tuning.err
 echo "tuning run exit $?"; date
 ls -la $OUT; wc -l $OUT/*.csv 2>/dev/null; head -5 $OUT/*.csv 2>/dev/null
