@@ -230,7 +230,8 @@ GPS_API int gps_sa_mlp_forward_bf16x3_pm(int b, int n, int npoint, int nsample, 
  * graph draw a fresh mask on every replay), NULL to use `seed` alone.
  * out (B, L, ld_o) bf16; lse (B,H,L) fp32 log-sum-exp of the logits (saved for backward).
  * bf16 MFMA with fp32 accumulation; softmax in fp32.  head_dim must be 64, L <= 512 (rows of more than 144
- * tokens stream their key chunks through a two-pass softmax instead of holding the whole score row). */
+ * tokens stream their key chunks through a two-pass softmax instead of holding the whole score row).  Spatial callers
+ * that can hand over the pairwise tensor as fp16 planes use gps_attn_forward_ex with pl_planes instead (up to 512 rows). */
 GPS_API int gps_attn_forward(int B, int H, int L, int head_dim, const void *q, const void *k, const void *v,
                              int ld_qkv, const float *sw, const float *pl, const unsigned char *mask,
                              float p_drop, unsigned long long seed, const void *seed_dev, void *out,
@@ -249,7 +250,8 @@ GPS_API void gps_attn_set_stream_min_tiles(int plain, int spatial);
  *      through LDS in 64-row blocks, online softmax; any length, variable-length batches, cross-attention),
  *   2  backward calls on them too (two launches: dQ per query block, dK / dV per key block; needs `out` and `delta_ws`),
  *   4  fixed-length self-attention up to 144 tokens on the K / V-resident kernels of gps_attention_sp.hip (one query strip
- *      per wave, probabilities and dS parked in LDS for the dK / dV pass: every score evaluated once).
+ *      per wave, probabilities and dS parked in LDS for the dK / dV pass: every score evaluated once).  Plain form only:
+ *      the spatial form's plane kernels (gps_attn_args.pl_planes, up to 512 rows) do not depend on this mask.
  * Calls no set bit covers take the whole-sequence kernels of gps_attention.hip.  Default 1 | 4 (measured, profiles/r5:
  * the block-streaming backward ties the whole-sequence one on the variable-length text batches).  All families share lse
  * and the dropout stream, so forward and backward may come from different ones.  mode < 0 = query.  Returns the previous
@@ -311,18 +313,23 @@ typedef struct gps_attn_args {
    * no contribution to dk / dv).  For consumers that read a sequence at a few leading rows only (a caption read at
    * [CLS] in its last layer).  NULL = every row. */
   const int *q_limit;
-  /* PLANE FORM of the spatial term (bf16 self-attention, Lq == Lk <= 144, p_drop == 0; replaces sw / pl / dsw, which
+  /* PLANE FORM of the spatial term (bf16 self-attention, Lq == Lk <= 512, p_drop == 0; replaces sw / pl / dsw, which
    * must then be NULL): pl_planes (B, 5, Lq, ld_pl) fp16 = the pairwise tensor as five planes, pl_planes[b][d][l][t] =
    * pl[b][l][t][d] (gps_pairwise_locs_planes / gps_pairwise_to_planes write it; ld_pl a multiple of 4 >= Lk, base 8-byte
    * aligned, columns >= Lk finite); sw16 = the conditioning vector in bf16, row (b, l) at sw16 + (b Lq + l) ld_sw, head h
    * at + 6 h (i.e. read in place from the packed projection output; ld_sw even); dsw16 / ld_dsw (backward): its
-   * gradient, bf16, addressed the same way.  Served by gps_attention_sp.hip: every
-   * operand of a query strip is requested at kernel entry, results leave as 8-byte stores. */
+   * gradient, bf16, addressed the same way.  Rows up to 144: gps_attention_sp.hip (K / V resident, every operand of a
+   * query strip requested at kernel entry, results leave as 8-byte stores).  Rows 145 .. 512: gps_attention_spl.hip (keys
+   * streamed through LDS in 64-row blocks, online softmax; backward in two launches, dQ per query block and dK / dV per
+   * key block, deterministic): its BACKWARD call also needs delta_ws below ((B, H, Lq) fp32 scratch, written with
+   * rowsum(P dP) by the first launch), else GPS_ERR_INVALID_ARGUMENT.  Rows above 512, dropout, fp32 operands and
+   * cu_rows: GPS_ERR_UNSUPPORTED. */
   const void *pl_planes; int ld_pl;
   const void *sw16; int ld_sw;
   void *dsw16; int ld_dsw;
   /* backward of the PLAIN form (no pairwise term), block-streaming kernels (gps_attention_fa.hip): (B, H, Lq) fp32
-   * scratch -- the dQ launch writes delta = rowsum(dout * out) per query, the dK / dV launch reads it.  NULL: the
+   * scratch -- the dQ launch writes delta = rowsum(dout * out) per query, the dK / dV launch reads it (also required by
+   * the PLANE form above 144 rows, see pl_planes).  NULL: the
    * backward call takes the whole-sequence kernels of gps_attention.hip instead (same results to bf16 rounding). */
   float *delta_ws;
 } gps_attn_args;

@@ -941,14 +941,16 @@ int launch_plain(const Params &P, bool backward, hipStream_t s) {
 
 namespace gps_attn {
 
-// the plane form of the spatial self-attention call (gps_attn_args.pl_planes): argument checks done by run_ex
+// the plane form of the spatial self-attention call (gps_attn_args.pl_planes): argument checks done by run_ex; rows
+// up to 144 on the kernels of this file, longer rows (up to 512) on the block-streaming ones of gps_attention_spl.hip
 int run_spatial_planes(const gps_attn_args *a, bool backward, hipStream_t s) {
-  if (a->Lq != a->Lk || a->Lk > 144 || a->p_drop != 0.f || a->dtype != GPS_ATTN_BF16 || a->cu_rows) return GPS_ERR_UNSUPPORTED;
+  if (a->Lq != a->Lk || a->Lk > 512 || a->p_drop != 0.f || a->dtype != GPS_ATTN_BF16 || a->cu_rows) return GPS_ERR_UNSUPPORTED;
   if (!a->sw16 || a->sw || a->ld_q != a->ld_kv || (a->ld_pl & 3) || a->ld_pl < a->Lk || (a->ld_sw & 1) || a->ld_sw < a->H * 6)
     return GPS_ERR_INVALID_ARGUMENT;
   if (((uintptr_t)a->pl_planes & 7) || ((uintptr_t)a->sw16 & 3)) return GPS_ERR_UNSUPPORTED;
   if (backward && (!a->dsw16 || (a->ld_dsw & 1) || a->ld_dsw < a->H * 6 || ((uintptr_t)a->dsw16 & 3) || a->ld_dq != a->ld_dkv))
     return GPS_ERR_INVALID_ARGUMENT;
+  if (a->Lk > 144) return run_spatial_planes_long(a, backward, s);   // keys streamed in blocks: gps_attention_spl.hip
   gps_attn_sp::Params P = {};
   P.B = a->B; P.H = a->H; P.L = a->Lk; P.nt = (a->Lk + 15) / 16;
   P.ld_qkv = a->ld_kv; P.ld_o = a->ld_o; P.ld_pl = a->ld_pl; P.ld_sw = a->ld_sw;

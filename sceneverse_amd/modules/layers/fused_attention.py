@@ -17,6 +17,7 @@ GPU only; there is no CPU path (the torch formulation in transformers.attention_
 """
 from __future__ import annotations
 
+import os
 from typing import Optional
 
 import torch
@@ -46,7 +47,11 @@ def _ptr(t: Optional[torch.Tensor]):
     return t.data_ptr() if t is not None else None
 
 
-MAX_LEN_PLANES = 144          # spatial self-attention rows served by gps_attention_sp.hip (plane form of the pairwise term)
+# spatial self-attention rows served by the plane form of the pairwise term: gps_attention_sp.hip up to 144 rows,
+# gps_attention_spl.hip (keys streamed in 64-row blocks) above.  GPS_SPATIAL_PLANES_MAX_L (read once, default 512) lowers
+# the bound: 144 gives the dispatch of the K / V-resident kernels alone (A/B runs of the stress preset).
+MAX_LEN_PLANES = max(0, min(512, int(os.environ.get("GPS_SPATIAL_PLANES_MAX_L", "512"))))
+_RESIDENT_PLANES = 144        # rows above this take the block-streaming plane kernels (their backward needs delta_ws)
 _PLANES = True                # False: the general kernels with the interleaved fp32 pairwise tensor (A/B runs, tests)
 
 
@@ -165,7 +170,8 @@ class _FusedSelfAttention(torch.autograd.Function):
                       q=base, ld_q=W, k=base + D * esz, v=base + 2 * D * esz, ld_kv=W, mask=_ptr(m8), p_drop=0.0, seed=0,
                       out=out, ld_o=D, lse=lse, dout=dout, dq=gbase, ld_dq=W, dk=gbase + D * esz, dv=gbase + 2 * D * esz,
                       ld_dkv=W, pl_planes=planes, ld_pl=planes.shape[-1], sw16=base + 3 * D * esz, ld_sw=W,
-                      dsw16=gbase + 3 * D * esz, ld_dsw=W)
+                      dsw16=gbase + 3 * D * esz, ld_dsw=W,
+                      delta_ws=_delta_ws(B, n_head, L, packed.device) if L > _RESIDENT_PLANES else None)
             return dpacked, None, None, None, None, None, None
         packed, sw, pl, m8, lse, seed_dev, out = ctx.saved_tensors
         B, L, W = packed.shape
@@ -294,7 +300,7 @@ class _FusedVarlenSelfAttention(torch.autograd.Function):
 
 def _delta_ws(n_seq: int, n_head: int, cap: int, device) -> torch.Tensor:
     """(n_seq, H, cap) fp32 scratch of the block-streaming backward (gps_attn_args.delta_ws): the dQ launch writes
-    rowsum(dout * out) per query, the dK / dV launch reads it."""
+    rowsum(dout * out) per query (plane form above 144 rows: rowsum(P dP) in fp32), the dK / dV launch reads it."""
     return torch.empty((n_seq, n_head, cap), dtype=torch.float32, device=device)
 
 
