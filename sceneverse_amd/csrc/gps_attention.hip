@@ -30,18 +30,16 @@
 #include <stdlib.h>
 
 #include "gps_hip.h"
+#include "gps_attention_dev.h"
+#include "gps_attention_run.h"
 #include "gps_device_flags.h"
-#include "gps_attention_ex.h"
+#include "gps_dropout.h"
 
 namespace gps_attn {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
+using namespace gps_attn_dev;
+using namespace gps_dropout;
 
-constexpr int DH = 64;        // head width (the only one the GPS configs use)
-constexpr int KS = DH + 8;    // LDS row pitch of row-major tiles, bf16 elements (144 B: conflict-free b128)
 constexpr int SD = 6;         // conditioning vector per (token, head): bias + 5 weights
 
 struct Params {
@@ -73,58 +71,9 @@ struct Params {
                                         // L / Lq are then the CAPACITY (longest sequence; LDS sizing, lse pitch)
 };
 
-__device__ __forceinline__ unsigned long long effective_seed(const Params &P) {
-  return P.seed + (P.seed_dev ? *P.seed_dev : 0ull);
-}
-
 __device__ __forceinline__ uint16_t f2bf(float f) {   // round to nearest even (hardware conversion)
   return __builtin_bit_cast(uint16_t, (__bf16)f);
 }
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
-__device__ __forceinline__ unsigned int pack2(float lo, float hi) {     // v_cvt_pk_bf16_f32: round to nearest even
-  const bf16x2_t h = {(__bf16)lo, (__bf16)hi};
-  return __builtin_bit_cast(unsigned int, h);
-}
-__device__ __forceinline__ bf16x8 as_frag(u32x4 v) { return __builtin_bit_cast(bf16x8, v); }
-__device__ __forceinline__ u32x4 zero4() { u32x4 z = {0u, 0u, 0u, 0u}; return z; }
-
-__device__ __forceinline__ f32x4 mfma(bf16x8 a, bf16x8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-
-// counter-based RNG for attention dropout (splitmix64 finaliser): the same (seed, element) gives the
-// same keep decision in forward and backward
-// Counter-based dropout stream of the attention kernels: a 32-bit avalanche hash (two multiplies, three
-// xor-shifts; "lowbias32" constants) of the element (or key-pair) index folded with the seed.  All that matters is
-// that forward and backward draw the same bits for the same (seed, index) and that the keep rate is 1 - p; a
-// 64-bit splitmix per element cost ~30 vector instructions of the ~45 these kernels spent per score.
-__device__ __forceinline__ unsigned int mix32(unsigned int x) {
-  x ^= x >> 16;
-  x *= 0x21F0AAADu;
-  x ^= x >> 15;
-  x *= 0x735A2D97u;
-  x ^= x >> 15;
-  return x;
-}
-__device__ __forceinline__ unsigned int seed_fold(unsigned long long seed) {      // wave-uniform
-  return mix32((unsigned int)seed ^ mix32((unsigned int)(seed >> 32) + 0x9E3779B9u));
-}
-__device__ __forceinline__ unsigned int rng_u32(unsigned long long seed, unsigned long long idx) {
-  return mix32(((unsigned int)idx + (unsigned int)(idx >> 32) * 0x85EBCA6Bu) ^ seed_fold(seed));
-}
-
-__device__ __forceinline__ void block_to_bh(const Params &P, int &b, int &h) {
-  const int id = blockIdx.x;
-  if ((P.B & 7) == 0) {       // heads of one scene on one XCD (block id mod 8), scenes spread over XCDs
-    const int xcd = id & 7, slot = id >> 3;
-    b = (slot / P.H) * 8 + xcd;
-    h = slot % P.H;
-  } else {
-    b = id / P.H;
-    h = id % P.H;
-  }
-}
-
 // rows [0, rows_total) of a (.., ld) bf16 matrix (64 columns of head h) -> LDS [rows_total][KS];
 // rows >= rows_valid are zero
 __device__ __forceinline__ void stage_rows(uint16_t *dst, const uint16_t *src, int ld, int rows_valid,
@@ -161,20 +110,6 @@ __device__ __forceinline__ bf16x8 frag_from_transposed(const uint16_t *t, int ts
   u32x4 v = {lo[0], lo[1], hi[0], hi[1]};
   return as_frag(v);
 }
-// pack the D fragments of two adjacent 16-row tiles into one A fragment (same K order as above)
-__device__ __forceinline__ bf16x8 pack_tiles(const f32x4 &a, const f32x4 &b) {
-  u32x4 v = {pack2(a[0], a[1]), pack2(a[2], a[3]), pack2(b[0], b[1]), pack2(b[2], b[3])};
-  return as_frag(v);
-}
-
-__device__ __forceinline__ float xor_reduce_max_rows(float v) {   // across the 4 lane groups
-  v = fmaxf(v, __shfl_xor(v, 16, 64));
-  return fmaxf(v, __shfl_xor(v, 32, 64));
-}
-__device__ __forceinline__ float xor_reduce_sum_rows(float v) {
-  v += __shfl_xor(v, 16, 64);
-  return v + __shfl_xor(v, 32, 64);
-}
 // spatial term of one (query, key) pair: z = w0 + sum_d w_d pl_d; sig = sigmoid(z);
 // returns log(clamp(sig, 1e-6)) (masked keys: log(1e-6)), and sig through `sig`.
 __device__ __forceinline__ float spatial_bias(const float *__restrict__ plp, const float (&w)[SD],
@@ -199,7 +134,7 @@ __global__ __launch_bounds__(512) void attn_fwd_kernel(const Params P) {
   uint8_t *s_mask = reinterpret_cast<uint8_t *>(Vt + 64 * TS);   // [NT*16] key-padding flags
 
   int b, h;
-  block_to_bh(P, b, h);
+  block_to_bh(P.B, P.H, b, h);
   const int L = P.L, nt = P.nt;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
   const int m = lane & 15, g = lane >> 4;
@@ -215,7 +150,7 @@ __global__ __launch_bounds__(512) void attn_fwd_kernel(const Params P) {
 
   const bool dropout = P.drop_thr != 0u;
   const float keep_scale = dropout ? 1.f / (1.f - P.p_drop) : 1.f;
-  const unsigned long long seed = dropout ? effective_seed(P) : 0ull;
+  const unsigned long long seed = dropout ? effective_seed(P.seed, P.seed_dev) : 0ull;
 
   for (int s = wave; s < nt; s += nwaves) {
     const int qi = 16 * s + m;              // this lane's query
@@ -236,7 +171,7 @@ __global__ __launch_bounds__(512) void attn_fwd_kernel(const Params P) {
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
           const u32x4 a = *reinterpret_cast<const u32x4 *>(Ks + (16 * j + m) * KS + 32 * c + 8 * g);
-          acc[j] = mfma(as_frag(a), bq[c], acc[j]);
+          acc[j] = mfma32(as_frag(a), bq[c], acc[j]);
         }
       }
     }
@@ -265,7 +200,7 @@ __global__ __launch_bounds__(512) void attn_fwd_kernel(const Params P) {
         mx = fmaxf(mx, x);
       }
     }
-    mx = xor_reduce_max_rows(mx);
+    mx = xor_max_g(mx);
     float sum = 0.f;
 #pragma unroll
     for (int j = 0; j < NT; ++j)
@@ -275,7 +210,7 @@ __global__ __launch_bounds__(512) void attn_fwd_kernel(const Params P) {
         acc[j][r] = p;
         sum += p;
       }
-    sum = xor_reduce_sum_rows(sum);
+    sum = xor_sum_g(sum);
     const float inv = 1.f / sum;
     if (g == 0 && q_ok) P.lse[((size_t)b * P.H + h) * L + qi] = mx + __logf(sum);
 #pragma unroll
@@ -300,7 +235,7 @@ __global__ __launch_bounds__(512) void attn_fwd_kernel(const Params P) {
         const f32x4 z = {0.f, 0.f, 0.f, 0.f};
         const bf16x8 pa = pack_tiles(acc[2 * c], (2 * c + 1 < NT) ? acc[(2 * c + 1 < NT) ? 2 * c + 1 : 0] : z);
 #pragma unroll
-        for (int n = 0; n < 4; ++n) o[n] = mfma(pa, frag_from_transposed(Vt, TS, n, c, lane), o[n]);
+        for (int n = 0; n < 4; ++n) o[n] = mfma32(pa, frag_from_transposed(Vt, TS, n, c, lane), o[n]);
       }
     }
     // o[n][r] = O[query 16 s + 4 g + r][d = 16 n + m]
@@ -334,7 +269,7 @@ __global__ __launch_bounds__(512) void attn_bwd_recompute_kernel(const Params P)
   float *delta_s = reinterpret_cast<float *>(smem + kBig);   // [NT*16]
 
   int b, h;
-  block_to_bh(P, b, h);
+  block_to_bh(P.B, P.H, b, h);
   const int L = P.L, nt = P.nt;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
   const int m = lane & 15, g = lane >> 4;
@@ -346,7 +281,7 @@ __global__ __launch_bounds__(512) void attn_bwd_recompute_kernel(const Params P)
   const float *lse = P.lse + ((size_t)b * P.H + h) * L;
   const bool dropout = P.drop_thr != 0u;
   const float keep_scale = dropout ? 1.f / (1.f - P.p_drop) : 1.f;
-  const unsigned long long seed = dropout ? effective_seed(P) : 0ull;
+  const unsigned long long seed = dropout ? effective_seed(P.seed, P.seed_dev) : 0ull;
 
   stage_rows(Ks, kb, P.ld_qkv, L, NT * 16);
   stage_rows(Vs, vb, P.ld_qkv, L, NT * 16);
@@ -378,8 +313,8 @@ __global__ __launch_bounds__(512) void attn_bwd_recompute_kernel(const Params P)
         for (int c = 0; c < 2; ++c) {
           const u32x4 a = *reinterpret_cast<const u32x4 *>(Ks + (16 * j + m) * KS + 32 * c + 8 * g);
           const u32x4 av = *reinterpret_cast<const u32x4 *>(Vs + (16 * j + m) * KS + 32 * c + 8 * g);
-          acc[j] = mfma(as_frag(a), bq[c], acc[j]);       // S^T
-          dacc[j] = mfma(as_frag(av), bdo[c], dacc[j]);   // (dO V^T)^T
+          acc[j] = mfma32(as_frag(a), bq[c], acc[j]);       // S^T
+          dacc[j] = mfma32(as_frag(av), bdo[c], dacc[j]);   // (dO V^T)^T
         }
       }
     }
@@ -417,7 +352,7 @@ __global__ __launch_bounds__(512) void attn_bwd_recompute_kernel(const Params P)
         dacc[j][r] = dp;
         delta += p * dp;
       }
-    delta = xor_reduce_sum_rows(delta);
+    delta = xor_sum_g(delta);
     if (g == 0) delta_s[16 * s + m] = delta;
     float dw[SD];
 #pragma unroll
@@ -441,7 +376,7 @@ __global__ __launch_bounds__(512) void attn_bwd_recompute_kernel(const Params P)
       }
     if (SPATIAL) {
 #pragma unroll
-      for (int d = 0; d < SD; ++d) dw[d] = xor_reduce_sum_rows(dw[d]);
+      for (int d = 0; d < SD; ++d) dw[d] = xor_sum_g(dw[d]);
       if (g == 0 && q_ok) {
 #pragma unroll
         for (int d = 0; d < SD; ++d) P.dsw[((row0 + qi) * P.H + h) * SD + d] = dw[d];
@@ -457,7 +392,7 @@ __global__ __launch_bounds__(512) void attn_bwd_recompute_kernel(const Params P)
         const f32x4 z = {0.f, 0.f, 0.f, 0.f};
         const bf16x8 da = pack_tiles(acc[2 * c], (2 * c + 1 < NT) ? acc[(2 * c + 1 < NT) ? 2 * c + 1 : 0] : z);
 #pragma unroll
-        for (int n = 0; n < 4; ++n) o[n] = mfma(da, frag_from_transposed(Kt, TS, n, c, lane), o[n]);
+        for (int n = 0; n < 4; ++n) o[n] = mfma32(da, frag_from_transposed(Kt, TS, n, c, lane), o[n]);
       }
     }
 #pragma unroll
@@ -514,8 +449,8 @@ __global__ __launch_bounds__(512) void attn_bwd_recompute_kernel(const Params P)
               v = *reinterpret_cast<const u32x4 *>(qb + (size_t)qa * P.ld_qkv + 32 * cc + 8 * g);
               u = *reinterpret_cast<const u32x4 *>(dob + (size_t)qa * P.ld_o + 32 * cc + 8 * g);
             }
-            sacc = mfma(as_frag(v), bk[cc], sacc);    // S[query 16 i + 4 g + r][key t]
-            dacc = mfma(as_frag(u), bv[cc], dacc);    // dO V^T
+            sacc = mfma32(as_frag(v), bk[cc], sacc);    // S[query 16 i + 4 g + r][key t]
+            dacc = mfma32(as_frag(u), bv[cc], dacc);    // dO V^T
           }
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
@@ -547,8 +482,8 @@ __global__ __launch_bounds__(512) void attn_bwd_recompute_kernel(const Params P)
       const bf16x8 da = pack_tiles(ds[0], ds[1]);
 #pragma unroll
       for (int n = 0; n < 4; ++n) {
-        dv[n] = mfma(pa, frag_from_transposed(dOt, TS, n, c, lane), dv[n]);
-        dk[n] = mfma(da, frag_from_transposed(Qt, TS, n, c, lane), dk[n]);
+        dv[n] = mfma32(pa, frag_from_transposed(dOt, TS, n, c, lane), dv[n]);
+        dk[n] = mfma32(da, frag_from_transposed(Qt, TS, n, c, lane), dk[n]);
       }
     }
 #pragma unroll
@@ -592,7 +527,7 @@ __global__ __launch_bounds__(512) void attn_bwd_kernel(const Params P) {
   uint8_t *s_mask = reinterpret_cast<uint8_t *>(dST + NT * 16 * TS);   // [NT*16] key-padding flags
 
   int b, h;
-  block_to_bh(P, b, h);
+  block_to_bh(P.B, P.H, b, h);
   const int L = P.L, nt = P.nt;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
   const int m = lane & 15, g = lane >> 4;
@@ -604,7 +539,7 @@ __global__ __launch_bounds__(512) void attn_bwd_kernel(const Params P) {
   const float *lse = P.lse + ((size_t)b * P.H + h) * L;
   const bool dropout = P.drop_thr != 0u;
   const float keep_scale = dropout ? 1.f / (1.f - P.p_drop) : 1.f;
-  const unsigned long long seed = dropout ? effective_seed(P) : 0ull;
+  const unsigned long long seed = dropout ? effective_seed(P.seed, P.seed_dev) : 0ull;
 
   stage_rows(Ks, kb, P.ld_qkv, L, NT * 16);
   stage_rows(Vs, vb, P.ld_qkv, L, NT * 16);
@@ -642,8 +577,8 @@ __global__ __launch_bounds__(512) void attn_bwd_kernel(const Params P) {
         for (int c = 0; c < 2; ++c) {
           const u32x4 a = *reinterpret_cast<const u32x4 *>(Ks + (16 * j + m) * KS + 32 * c + 8 * g);
           const u32x4 av = *reinterpret_cast<const u32x4 *>(Vs + (16 * j + m) * KS + 32 * c + 8 * g);
-          acc[j] = mfma(as_frag(a), bq[c], acc[j]);
-          dacc[j] = mfma(as_frag(av), bdo[c], dacc[j]);
+          acc[j] = mfma32(as_frag(a), bq[c], acc[j]);
+          dacc[j] = mfma32(as_frag(av), bdo[c], dacc[j]);
         }
       }
     }
@@ -679,7 +614,7 @@ __global__ __launch_bounds__(512) void attn_bwd_kernel(const Params P) {
         dacc[j][r] = dp;
         delta += p * dp;
       }
-    delta = xor_reduce_sum_rows(delta);
+    delta = xor_sum_g(delta);
     float dw[SD];
 #pragma unroll
     for (int d = 0; d < SD; ++d) dw[d] = 0.f;
@@ -708,7 +643,7 @@ __global__ __launch_bounds__(512) void attn_bwd_kernel(const Params P) {
       }
     if (SPATIAL) {
 #pragma unroll
-      for (int d = 0; d < SD; ++d) dw[d] = xor_reduce_sum_rows(dw[d]);
+      for (int d = 0; d < SD; ++d) dw[d] = xor_sum_g(dw[d]);
       if (g == 0 && q_ok) {
 #pragma unroll
         for (int d = 0; d < SD; ++d) P.dsw[((row0 + qi) * P.H + h) * SD + d] = dw[d];
@@ -723,7 +658,7 @@ __global__ __launch_bounds__(512) void attn_bwd_kernel(const Params P) {
         const f32x4 z = {0.f, 0.f, 0.f, 0.f};
         const bf16x8 da = pack_tiles(acc[2 * c], (2 * c + 1 < NT) ? acc[(2 * c + 1 < NT) ? 2 * c + 1 : 0] : z);
 #pragma unroll
-        for (int n = 0; n < 4; ++n) o[n] = mfma(da, frag_from_transposed(Kt, TS, n, c, lane), o[n]);
+        for (int n = 0; n < 4; ++n) o[n] = mfma32(da, frag_from_transposed(Kt, TS, n, c, lane), o[n]);
       }
     }
 #pragma unroll
@@ -760,8 +695,8 @@ __global__ __launch_bounds__(512) void attn_bwd_kernel(const Params P) {
         for (int n = 0; n < 4; ++n) {
           const bf16x8 bo = as_frag(*reinterpret_cast<const u32x4 *>(dOt + (16 * n + m) * TS + 32 * c + 8 * g));
           const bf16x8 bqf = as_frag(*reinterpret_cast<const u32x4 *>(Qt + (16 * n + m) * TS + 32 * c + 8 * g));
-          dv[n] = mfma(pa, bo, dv[n]);
-          dk[n] = mfma(da, bqf, dk[n]);
+          dv[n] = mfma32(pa, bo, dv[n]);
+          dk[n] = mfma32(da, bqf, dk[n]);
         }
       }
     }
@@ -793,38 +728,11 @@ __global__ __launch_bounds__(512) void attn_bwd_kernel(const Params P) {
 // K and V stay ROW-major in LDS and serve both operand kinds: A fragments by 16-byte reads, B fragments by the
 // hardware-transposed ds_read_b64_tr_b16 (no transposing stores, no V^T / K^T tiles).
 // ==========================================================================================
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-
-// dropout of the streaming kernels: ONE hash per pair of adjacent keys (t even, t odd) of a query, its low / high
-// 16 bits decide the two elements (threshold p * 2^16: the drop probability is quantised to 1 / 65536).  The three
-// places that need the mask (forward pass B, both backward passes) evaluate the same function of (query, key pair).
-// one hash decides the two keys of a pair (16-bit thresholds): index of the pair = (row base + key) / 2 with an even
-// row pitch, so that the lane holding keys (4 g + 0..3) of a query needs two hashes
-__device__ __forceinline__ unsigned int pair_rng(unsigned int seedmix, unsigned int row_pair_base, int t) {
-  return mix32((row_pair_base + (unsigned int)(t >> 1)) ^ seedmix);
-}
-__device__ __forceinline__ bool pair_keep(unsigned int r, int t, unsigned int thr16) {
-  return ((t & 1) ? (r >> 16) : (r & 0xFFFFu)) >= thr16;
-}
-constexpr float kLog2e = 1.4426950408889634f;
-constexpr float kLn2 = 0.6931471805599453f;
-
-// B fragment (32 keys x 16 columns, K order of pack_tiles) from a row-major [key][KS] tile
-__device__ __forceinline__ bf16x8 frag_from_rows_tr(const uint16_t *rows, int ntile, int c, int lane) {
-  const int i = lane & 15, g = lane >> 4;
-  const uint16_t *p = rows + (32 * c + 4 * g + (i >> 2)) * KS + 16 * ntile + 4 * (i & 3);
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4 *)p);
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4 *)(p + 16 * KS));
-  const u32x2 l2 = __builtin_bit_cast(u32x2, lo), h2 = __builtin_bit_cast(u32x2, hi);
-  const u32x4 v = {l2[0], l2[1], h2[0], h2[1]};
-  return as_frag(v);
-}
-
 template <bool SPATIAL>
 __global__ __launch_bounds__(1024) void attn_fwd_stream_kernel(const Params P) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   int b, h;
-  block_to_bh(P, b, h);
+  block_to_bh(P.B, P.H, b, h);
   if (P.seq_order) b = P.seq_order[b];
   // fixed-length batch: sequence b = rows [b L, b L + L); packed variable-length batch: rows [cu[b], cu[b + 1])
   int L = P.L, Lq = P.Lq;
@@ -854,7 +762,7 @@ __global__ __launch_bounds__(1024) void attn_fwd_stream_kernel(const Params P) {
 
   const bool dropout = P.drop_thr != 0u;
   const float keep_scale = dropout ? 1.f / (1.f - P.p_drop) : 1.f;
-  const unsigned int seedmix = dropout ? seed_fold(effective_seed(P)) : 0u;
+  const unsigned int seedmix = dropout ? seed_fold(effective_seed(P.seed, P.seed_dev)) : 0u;
   const unsigned int thr16 = P.drop_thr >> 16;
   const unsigned int pitch2 = (unsigned int)((P.L + 1) >> 1);     // key pairs per query row (capacity: the same in backward)
 
@@ -880,7 +788,7 @@ __global__ __launch_bounds__(1024) void attn_fwd_stream_kernel(const Params P) {
 #pragma unroll
       for (int c = 0; c < 2; ++c) {
         const u32x4 a = *reinterpret_cast<const u32x4 *>(Ks + (16 * j + m) * KS + 32 * c + 8 * g);
-        acc = mfma(as_frag(a), bq[c], acc);
+        acc = mfma32(as_frag(a), bq[c], acc);
       }
       const f32x4 kt = *reinterpret_cast<const f32x4 *>(mb + 16 * j + 4 * g);
 #pragma unroll
@@ -905,7 +813,7 @@ __global__ __launch_bounds__(1024) void attn_fwd_stream_kernel(const Params P) {
       logits2(j, x);
       mx = fmaxf(mx, fmaxf(fmaxf(x[0], x[1]), fmaxf(x[2], x[3])));
     }
-    const float gmx = xor_reduce_max_rows(mx);
+    const float gmx = xor_max_g(mx);
     // pass B: p = 2^(x - max) chunk by chunk; the normaliser accumulates beside the P V product and is applied,
     // with the dropout scale, to the 16 x 64 output strip at the end
     const unsigned int rp = (((unsigned int)b * P.H + h) * Lq_cap + qi) * pitch2;
@@ -937,9 +845,9 @@ __global__ __launch_bounds__(1024) void attn_fwd_stream_kernel(const Params P) {
       }
       const bf16x8 pa = pack_tiles(pt[0], pt[1]);
 #pragma unroll
-      for (int n = 0; n < 4; ++n) o[n] = mfma(pa, frag_from_rows_tr(Vs, n, c, lane), o[n]);
+      for (int n = 0; n < 4; ++n) o[n] = mfma32(pa, tr_frag_perm(Vs, KS, c, 16 * n, lane), o[n]);
     }
-    lsum = xor_reduce_sum_rows(lsum);             // all keys masked -> NaN row, like torch
+    lsum = xor_sum_g(lsum);             // all keys masked -> NaN row, like torch
     if (g == 0 && q_ok) P.lse[((size_t)b * P.H + h) * Lq_cap + qi] = (gmx + __builtin_amdgcn_logf(lsum)) * kLn2;
     const float scale_q = keep_scale / lsum;      // of query 16 s + m; the output rows of this lane are 4 g + r
 #pragma unroll
@@ -959,7 +867,7 @@ template <bool SPATIAL>
 __global__ __launch_bounds__(1024) void attn_bwd_stream_kernel(const Params P) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   int b, h;
-  block_to_bh(P, b, h);
+  block_to_bh(P.B, P.H, b, h);
   if (P.seq_order) b = P.seq_order[b];
   int L = P.L, Lq = P.Lq;
   size_t row0 = (size_t)b * P.L, row0q = (size_t)b * P.Lq;
@@ -993,7 +901,7 @@ __global__ __launch_bounds__(1024) void attn_bwd_stream_kernel(const Params P) {
   const float *lse = P.lse + ((size_t)b * P.H + h) * Lq_cap;
   const bool dropout = P.drop_thr != 0u;
   const float keep_scale = dropout ? 1.f / (1.f - P.p_drop) : 1.f;
-  const unsigned int seedmix = dropout ? seed_fold(effective_seed(P)) : 0u;
+  const unsigned int seedmix = dropout ? seed_fold(effective_seed(P.seed, P.seed_dev)) : 0u;
   const unsigned int thr16 = P.drop_thr >> 16;
   const unsigned int pitch2 = (unsigned int)((P.L + 1) >> 1);
   const unsigned int bh_base = ((unsigned int)b * P.H + h) * Lq_cap;
@@ -1060,8 +968,8 @@ __global__ __launch_bounds__(1024) void attn_bwd_stream_kernel(const Params P) {
           for (int cc = 0; cc < 2; ++cc) {
             const u32x4 a = *reinterpret_cast<const u32x4 *>(Ks + (16 * j + m) * KS + 32 * cc + 8 * g);
             const u32x4 av = *reinterpret_cast<const u32x4 *>(Vs + (16 * j + m) * KS + 32 * cc + 8 * g);
-            acc = mfma(as_frag(a), bq[cc], acc);        // S^T
-            dacc = mfma(as_frag(av), bdo[cc], dacc);    // (dO V^T)^T
+            acc = mfma32(as_frag(a), bq[cc], acc);        // S^T
+            dacc = mfma32(as_frag(av), bdo[cc], dacc);    // (dO V^T)^T
           }
           const int t0 = 16 * j + 4 * g;
           const f32x4 kt = *reinterpret_cast<const f32x4 *>(mb + t0);
@@ -1105,11 +1013,11 @@ __global__ __launch_bounds__(1024) void attn_bwd_stream_kernel(const Params P) {
       }
       const bf16x8 da = pack_tiles(ds[0], ds[1]);
 #pragma unroll
-      for (int n = 0; n < 4; ++n) o[n] = mfma(da, frag_from_rows_tr(Ks, n, c, lane), o[n]);
+      for (int n = 0; n < 4; ++n) o[n] = mfma32(da, tr_frag_perm(Ks, KS, c, 16 * n, lane), o[n]);
     }
     if (SPATIAL) {
 #pragma unroll
-      for (int d = 0; d < SD; ++d) dw[d] = xor_reduce_sum_rows(dw[d]);
+      for (int d = 0; d < SD; ++d) dw[d] = xor_sum_g(dw[d]);
       if (g == 0 && q_ok) {
 #pragma unroll
         for (int d = 0; d < SD; ++d) P.dsw[((row0q + qi) * P.H + h) * SD + d] = dw[d];
@@ -1171,8 +1079,8 @@ __global__ __launch_bounds__(1024) void attn_bwd_stream_kernel(const Params P) {
           for (int cc = 0; cc < 2; ++cc) {
             const u32x4 v = *reinterpret_cast<const u32x4 *>(Qs + (16 * i + m) * KS + 32 * cc + 8 * g);
             const u32x4 u = *reinterpret_cast<const u32x4 *>(dOs + (16 * i + m) * KS + 32 * cc + 8 * g);
-            sacc = mfma(as_frag(v), bk[cc], sacc);    // S[query 16 i + 4 g + r][key t]
-            dacc = mfma(as_frag(u), bv[cc], dacc);    // dO V^T
+            sacc = mfma32(as_frag(v), bk[cc], sacc);    // S[query 16 i + 4 g + r][key t]
+            dacc = mfma32(as_frag(u), bv[cc], dacc);    // dO V^T
           }
           const int q0 = 16 * i + 4 * g;
           const f32x4 lq = *reinterpret_cast<const f32x4 *>(lse_s + q0);
@@ -1220,8 +1128,8 @@ __global__ __launch_bounds__(1024) void attn_bwd_stream_kernel(const Params P) {
       const bf16x8 da = pack_tiles(ds[0], ds[1]);
 #pragma unroll
       for (int n = 0; n < 4; ++n) {
-        dv[n] = mfma(pa, frag_from_rows_tr(dOs, n, c, lane), dv[n]);
-        dk[n] = mfma(da, frag_from_rows_tr(Qs, n, c, lane), dk[n]);
+        dv[n] = mfma32(pa, tr_frag_perm(dOs, KS, c, 16 * n, lane), dv[n]);
+        dk[n] = mfma32(da, tr_frag_perm(Qs, KS, c, 16 * n, lane), dk[n]);
       }
     }
 #pragma unroll
@@ -1265,12 +1173,7 @@ int launch_stream(const Params &P, bool backward, hipStream_t s) {
   const void *fn = backward ? (spatial ? (const void *)&attn_bwd_stream_kernel<true> : (const void *)&attn_bwd_stream_kernel<false>)
                             : (spatial ? (const void *)&attn_fwd_stream_kernel<true> : (const void *)&attn_fwd_stream_kernel<false>);
   static gps_dev::PerDevice<size_t, 4> granted_dev;
-  size_t *granted = granted_dev.row();
-  const int slot = (backward ? 2 : 0) + (spatial ? 1 : 0);
-  if (lds > 64 * 1024 && lds > granted[slot]) {
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return GPS_ERR_LAUNCH;
-    granted[slot] = 160 * 1024;
-  }
+  if (gps_dev::grant_lds(fn, lds, 160 * 1024, granted_dev.row()[(backward ? 2 : 0) + (spatial ? 1 : 0)]) != GPS_OK) return GPS_ERR_LAUNCH;
   if (backward) {
     if (spatial) hipLaunchKernelGGL((attn_bwd_stream_kernel<true>), grid, block, lds, s, P);
     else hipLaunchKernelGGL((attn_bwd_stream_kernel<false>), grid, block, lds, s, P);
@@ -1310,21 +1213,13 @@ int launch(const Params &P, bool backward, hipStream_t s) {
   const bool spatial = P.sw != nullptr;
   const bool resident = bwd_lds<NT>() <= kLdsMax;     // P^T / dS^T fit LDS
   const size_t lds = backward ? (resident ? bwd_lds<NT>() : bwd_recompute_lds<NT>()) : fwd_lds<NT>();
-  if (lds > 64 * 1024) {
-    static gps_dev::PerDevice<bool, 4> done_dev;
-    bool *done = done_dev.row();
-    const int slot = (backward ? 2 : 0) + (spatial ? 1 : 0);
-    if (!done[slot]) {
-      const void *fn =
-          backward ? (resident ? (spatial ? (const void *)&attn_bwd_kernel<NT, true> : (const void *)&attn_bwd_kernel<NT, false>)
-                               : (spatial ? (const void *)&attn_bwd_recompute_kernel<NT, true>
-                                          : (const void *)&attn_bwd_recompute_kernel<NT, false>))
-                   : (spatial ? (const void *)&attn_fwd_kernel<NT, true> : (const void *)&attn_fwd_kernel<NT, false>);
-      if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return GPS_ERR_LAUNCH;
-      done[slot] = true;
-    }
-  }
+  const void *fn =
+      backward ? (resident ? (spatial ? (const void *)&attn_bwd_kernel<NT, true> : (const void *)&attn_bwd_kernel<NT, false>)
+                           : (spatial ? (const void *)&attn_bwd_recompute_kernel<NT, true>
+                                      : (const void *)&attn_bwd_recompute_kernel<NT, false>))
+               : (spatial ? (const void *)&attn_fwd_kernel<NT, true> : (const void *)&attn_fwd_kernel<NT, false>);
+  static gps_dev::PerDevice<size_t, 4> granted_dev;
+  if (gps_dev::grant_lds(fn, lds, lds, granted_dev.row()[(backward ? 2 : 0) + (spatial ? 1 : 0)]) != GPS_OK) return GPS_ERR_LAUNCH;
   if (backward && resident) {
     if (spatial) hipLaunchKernelGGL((attn_bwd_kernel<NT, true>), grid, block, lds, s, P);
     else hipLaunchKernelGGL((attn_bwd_kernel<NT, false>), grid, block, lds, s, P);
@@ -1424,7 +1319,7 @@ int run_ex(const gps_attn_args *a, bool backward, hipStream_t s) {
   P.q = (const uint16_t *)a->q; P.k = (const uint16_t *)a->k; P.v = (const uint16_t *)a->v;
   P.sw = a->sw; P.pl = a->pl; P.mask = a->mask; P.out = (uint16_t *)a->out; P.lse = a->lse;
   P.p_drop = a->p_drop; P.seed = a->seed; P.seed_dev = (const unsigned long long *)a->seed_dev;
-  P.drop_thr = a->p_drop > 0.f ? (unsigned int)((double)a->p_drop * 4294967296.0) : 0u;
+  P.drop_thr = gps_dropout::drop_threshold(a->p_drop);
   P.cu_rows = a->cu_rows;
   P.seq_order = a->cu_rows ? a->seq_order : nullptr;
   P.q_limit = a->cu_rows ? a->q_limit : nullptr;
@@ -1474,7 +1369,7 @@ int gps_attn_forward(int B, int H, int L, int head_dim, const void *q, const voi
   P.q = (const uint16_t *)q; P.k = (const uint16_t *)k; P.v = (const uint16_t *)v;
   P.sw = sw; P.pl = pl; P.mask = mask; P.out = (uint16_t *)out; P.lse = lse;
   P.p_drop = p_drop; P.seed = seed; P.seed_dev = (const unsigned long long *)seed_dev;
-  P.drop_thr = p_drop > 0.f ? (unsigned int)((double)p_drop * 4294967296.0) : 0u;
+  P.drop_thr = gps_dropout::drop_threshold(p_drop);
   return gps_attn::dispatch(P, false, (hipStream_t)stream);
 }
 
@@ -1497,7 +1392,7 @@ int gps_attn_backward(int B, int H, int L, int head_dim, const void *q, const vo
   P.dout = (const uint16_t *)dout; P.dq = (uint16_t *)dq; P.dk = (uint16_t *)dk; P.dv = (uint16_t *)dv;
   P.out = (uint16_t *)const_cast<void *>(out);
   P.dsw = dsw; P.p_drop = p_drop; P.seed = seed; P.seed_dev = (const unsigned long long *)seed_dev;
-  P.drop_thr = p_drop > 0.f ? (unsigned int)((double)p_drop * 4294967296.0) : 0u;
+  P.drop_thr = gps_dropout::drop_threshold(p_drop);
   return gps_attn::dispatch(P, true, (hipStream_t)stream);
 }
 

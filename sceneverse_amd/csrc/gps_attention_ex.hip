@@ -18,22 +18,20 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "gps_attention_ex.h"
-#include "gps_hip.h"
+#include "gps_attention_dev.h"
+#include "gps_attention_run.h"
 #include "gps_device_flags.h"
+#include "gps_dropout.h"
+#include "gps_hip.h"
 
 namespace gps_attn {
 namespace x {
 
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
+using namespace gps_attn_dev;      // vector types, DH, kLog2e / kLn2, block_to_bh, the lane-group reductions
+using namespace gps_dropout;
 
-constexpr int DH = 64;
 constexpr int SD = 6;
 constexpr int KSF = DH + 4;        // fp32 LDS row pitch (272 B, 16-byte aligned)
-constexpr float kLog2e = 1.4426950408889634f;
-constexpr float kLn2 = 0.6931471805599453f;
 
 struct PX {
   int B, H, Lq, Lk, ntq, ntk;
@@ -52,45 +50,6 @@ struct PX {
   const unsigned long long *seed_dev;
 };
 
-// ---- the dropout stream of gps_attention.hip's streaming kernels (same function of (seed, query, key pair)) ----
-__device__ __forceinline__ unsigned int mix32(unsigned int x) {
-  x ^= x >> 16;
-  x *= 0x21F0AAADu;
-  x ^= x >> 15;
-  x *= 0x735A2D97u;
-  x ^= x >> 15;
-  return x;
-}
-__device__ __forceinline__ unsigned int seed_fold(unsigned long long seed) {
-  return mix32((unsigned int)seed ^ mix32((unsigned int)(seed >> 32) + 0x9E3779B9u));
-}
-__device__ __forceinline__ unsigned int pair_rng(unsigned int seedmix, unsigned int row_pair_base, int t) {
-  return mix32((row_pair_base + (unsigned int)(t >> 1)) ^ seedmix);
-}
-__device__ __forceinline__ bool pair_keep(unsigned int r, int t, unsigned int thr16) {
-  return ((t & 1) ? (r >> 16) : (r & 0xFFFFu)) >= thr16;
-}
-__device__ __forceinline__ unsigned long long effective_seed(const PX &P) { return P.seed + (P.seed_dev ? *P.seed_dev : 0ull); }
-
-__device__ __forceinline__ void block_to_bh(const PX &P, int &b, int &h) {
-  const int id = blockIdx.x;
-  if ((P.B & 7) == 0) {       // heads of one scene on one XCD: they share the pairwise tensor in its L2
-    const int xcd = id & 7, slot = id >> 3;
-    b = (slot / P.H) * 8 + xcd;
-    h = slot % P.H;
-  } else {
-    b = id / P.H;
-    h = id % P.H;
-  }
-}
-__device__ __forceinline__ float xor_reduce_max_rows(float v) {
-  v = fmaxf(v, __shfl_xor(v, 16, 64));
-  return fmaxf(v, __shfl_xor(v, 32, 64));
-}
-__device__ __forceinline__ float xor_reduce_sum_rows(float v) {
-  v += __shfl_xor(v, 16, 64);
-  return v + __shfl_xor(v, 32, 64);
-}
 // z = w0 + sum_d w_d pl_d; returns log(clamp(sigmoid(z), 1e-6)) (masked keys: log(1e-6)); sig through `sig`.
 // Full-precision expf / logf: this is the fp32 parity path.
 __device__ __forceinline__ float spatial_bias(const float *__restrict__ plp, const float (&w)[SD], bool key_masked, float &sig) {
@@ -123,7 +82,7 @@ __global__ __launch_bounds__(1024) void attn_f32_fwd_kernel(const PX P) {
   float *Vs = Ks + rows * KSF;                        // [rows][KSF]
   float *mb = Vs + rows * KSF;                        // [rows] additive key term: 0, or -inf (padded / past Lk)
   int b, h;
-  block_to_bh(P, b, h);
+  block_to_bh(P.B, P.H, b, h);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
   const int m = lane & 15, g = lane >> 4;
   const size_t row0k = (size_t)b * Lk, row0q = (size_t)b * Lq;
@@ -138,7 +97,7 @@ __global__ __launch_bounds__(1024) void attn_f32_fwd_kernel(const PX P) {
 
   const bool dropout = P.drop_thr != 0u;
   const float keep_scale = dropout ? 1.f / (1.f - P.p_drop) : 1.f;
-  const unsigned int seedmix = dropout ? seed_fold(effective_seed(P)) : 0u;
+  const unsigned int seedmix = dropout ? seed_fold(effective_seed(P.seed, P.seed_dev)) : 0u;
   const unsigned int thr16 = P.drop_thr >> 16;
   const unsigned int pitch2 = (unsigned int)((Lk + 1) >> 1);
 
@@ -177,7 +136,7 @@ __global__ __launch_bounds__(1024) void attn_f32_fwd_kernel(const PX P) {
       logits2(j, x);
       mx = fmaxf(mx, fmaxf(fmaxf(x[0], x[1]), fmaxf(x[2], x[3])));
     }
-    const float gmx = xor_reduce_max_rows(mx);
+    const float gmx = xor_max_g(mx);
     const unsigned int rp = (((unsigned int)b * P.H + h) * Lq + qi) * pitch2;
     float lsum = 0.f;
     f32x4 o[4];
@@ -205,7 +164,7 @@ __global__ __launch_bounds__(1024) void attn_f32_fwd_kernel(const PX P) {
         for (int n = 0; n < 4; ++n) o[n] = mfma4(pt[r], vr[16 * n], o[n]);
       }
     }
-    lsum = xor_reduce_sum_rows(lsum);
+    lsum = xor_sum_g(lsum);
     if (g == 0 && q_ok) P.lse[((size_t)b * P.H + h) * Lq + qi] = (gmx + log2f(lsum)) * kLn2;
     const float scale_q = keep_scale / lsum;      // of query 16 s + m; the output rows of this lane are 4 g + r
 #pragma unroll
@@ -236,7 +195,7 @@ __global__ __launch_bounds__(1024) void attn_f32_bwd_kernel(const PX P) {
   float *lse_s = delta_s + rows_q;                     // [rows_q] log2(e) * lse, +inf past Lq
   float *mb = lse_s + rows_q;                          // [rows]
   int b, h;
-  block_to_bh(P, b, h);
+  block_to_bh(P.B, P.H, b, h);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
   const int m = lane & 15, g = lane >> 4;
   const size_t row0k = (size_t)b * Lk, row0q = (size_t)b * Lq;
@@ -251,7 +210,7 @@ __global__ __launch_bounds__(1024) void attn_f32_bwd_kernel(const PX P) {
   const float *lse = P.lse + ((size_t)b * P.H + h) * Lq;
   const bool dropout = P.drop_thr != 0u;
   const float keep_scale = dropout ? 1.f / (1.f - P.p_drop) : 1.f;
-  const unsigned int seedmix = dropout ? seed_fold(effective_seed(P)) : 0u;
+  const unsigned int seedmix = dropout ? seed_fold(effective_seed(P.seed, P.seed_dev)) : 0u;
   const unsigned int thr16 = P.drop_thr >> 16;
   const unsigned int pitch2 = (unsigned int)((Lk + 1) >> 1);
   const unsigned int bh_base = ((unsigned int)b * P.H + h) * Lq;
@@ -341,7 +300,7 @@ __global__ __launch_bounds__(1024) void attn_f32_bwd_kernel(const PX P) {
     }
     if (SPATIAL) {
 #pragma unroll
-      for (int d = 0; d < SD; ++d) dw[d] = xor_reduce_sum_rows(dw[d]);
+      for (int d = 0; d < SD; ++d) dw[d] = xor_sum_g(dw[d]);
       if (g == 0 && q_ok) {
 #pragma unroll
         for (int d = 0; d < SD; ++d) P.dsw[((row0q + qi) * P.H + h) * SD + d] = dw[d];
@@ -482,7 +441,7 @@ __global__ __launch_bounds__(1024) void attn_fp8_fwd_kernel(const PX P) {
   float *mb = reinterpret_cast<float *>(V8t + 64 * TS8);     // [rows]
   float *red = mb + rows;                                    // [2][16] per-wave amax of K, V; then [0], [16] hold the tile scales
   int b, h;
-  block_to_bh(P, b, h);
+  block_to_bh(P.B, P.H, b, h);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
   const int m = lane & 15, g = lane >> 4;
   const size_t row0k = (size_t)b * Lk, row0q = (size_t)b * Lq;
@@ -541,7 +500,7 @@ __global__ __launch_bounds__(1024) void attn_fp8_fwd_kernel(const PX P) {
 
   const bool dropout = P.drop_thr != 0u;
   const float keep_scale = dropout ? 1.f / (1.f - P.p_drop) : 1.f;
-  const unsigned int seedmix = dropout ? seed_fold(effective_seed(P)) : 0u;
+  const unsigned int seedmix = dropout ? seed_fold(effective_seed(P.seed, P.seed_dev)) : 0u;
   const unsigned int thr16 = P.drop_thr >> 16;
   const unsigned int pitch2 = (unsigned int)((Lk + 1) >> 1);
 
@@ -557,7 +516,7 @@ __global__ __launch_bounds__(1024) void attn_fp8_fwd_kernel(const PX P) {
       if (q_ok) qv[c] = *reinterpret_cast<const u32x4 *>(qb + (size_t)qi * P.ld_q + 32 * c + 8 * g);
       aq = fmaxf(aq, amax8(qv[c]));
     }
-    aq = xor_reduce_max_rows(aq);                   // the 64 features of a query row sit in lanes m + 16 g'
+    aq = xor_max_g(aq);                   // the 64 features of a query row sit in lanes m + 16 g'
     const float sq = aq > 0.f ? aq / kFp8Max : 1.f, rq = 1.f / sq;
     unsigned long long bq[2];
 #pragma unroll
@@ -601,7 +560,7 @@ __global__ __launch_bounds__(1024) void attn_fp8_fwd_kernel(const PX P) {
       logits2(j, x);
       mx = fmaxf(mx, fmaxf(fmaxf(x[0], x[1]), fmaxf(x[2], x[3])));
     }
-    const float gmx = xor_reduce_max_rows(mx);
+    const float gmx = xor_max_g(mx);
     const unsigned int rp = (((unsigned int)b * P.H + h) * Lq + qi) * pitch2;
     float lsum = 0.f;
     f32x4 o[4];
@@ -641,7 +600,7 @@ __global__ __launch_bounds__(1024) void attn_fp8_fwd_kernel(const PX P) {
         o[n] = mfma_fp8(pa, ((unsigned long long)vhi << 32) | vlo, o[n]);
       }
     }
-    lsum = xor_reduce_sum_rows(lsum);
+    lsum = xor_sum_g(lsum);
     if (g == 0 && q_ok) P.lse[((size_t)b * P.H + h) * Lq + qi] = (gmx + __builtin_amdgcn_logf(lsum)) * kLn2;
     const float scale_q = keep_scale * sV * (1.f / kPScale) / lsum;
 #pragma unroll
@@ -665,17 +624,8 @@ PX make_px(const gps_attn_args *a) {
   P.q = a->q; P.k = a->k; P.v = a->v; P.sw = a->sw; P.pl = a->pl; P.mask = a->mask;
   P.out = a->out; P.lse = a->lse; P.dout = a->dout; P.dq = a->dq; P.dk = a->dk; P.dv = a->dv; P.dsw = a->dsw;
   P.p_drop = a->p_drop; P.seed = a->seed; P.seed_dev = (const unsigned long long *)a->seed_dev;
-  P.drop_thr = a->p_drop > 0.f ? (unsigned int)((double)a->p_drop * 4294967296.0) : 0u;
+  P.drop_thr = gps_dropout::drop_threshold(a->p_drop);
   return P;
-}
-
-template <typename K>
-int set_lds(K kernel, size_t lds, size_t &granted) {
-  if (lds > 64 * 1024 && lds > granted) {
-    if (hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return GPS_ERR_LAUNCH;
-    granted = 160 * 1024;
-  }
-  return GPS_OK;
 }
 
 }  // namespace x
@@ -696,18 +646,18 @@ int run_f32(const gps_attn_args *a, bool backward, hipStream_t s) {
   int st;
   if (backward) {
     if (spatial) {
-      if ((st = set_lds(&attn_f32_bwd_kernel<true>, lds, granted[3])) != GPS_OK) return st;
+      if ((st = gps_dev::grant_lds((const void *)&attn_f32_bwd_kernel<true>, lds, 160 * 1024, granted[3])) != GPS_OK) return st;
       hipLaunchKernelGGL((attn_f32_bwd_kernel<true>), grid, block, lds, s, P);
     } else {
-      if ((st = set_lds(&attn_f32_bwd_kernel<false>, lds, granted[2])) != GPS_OK) return st;
+      if ((st = gps_dev::grant_lds((const void *)&attn_f32_bwd_kernel<false>, lds, 160 * 1024, granted[2])) != GPS_OK) return st;
       hipLaunchKernelGGL((attn_f32_bwd_kernel<false>), grid, block, lds, s, P);
     }
   } else {
     if (spatial) {
-      if ((st = set_lds(&attn_f32_fwd_kernel<true>, lds, granted[1])) != GPS_OK) return st;
+      if ((st = gps_dev::grant_lds((const void *)&attn_f32_fwd_kernel<true>, lds, 160 * 1024, granted[1])) != GPS_OK) return st;
       hipLaunchKernelGGL((attn_f32_fwd_kernel<true>), grid, block, lds, s, P);
     } else {
-      if ((st = set_lds(&attn_f32_fwd_kernel<false>, lds, granted[0])) != GPS_OK) return st;
+      if ((st = gps_dev::grant_lds((const void *)&attn_f32_fwd_kernel<false>, lds, 160 * 1024, granted[0])) != GPS_OK) return st;
       hipLaunchKernelGGL((attn_f32_fwd_kernel<false>), grid, block, lds, s, P);
     }
   }
@@ -726,10 +676,10 @@ int run_fp8_forward(const gps_attn_args *a, hipStream_t s) {
   size_t *granted = granted_dev.row();
   int st;
   if (P.sw != nullptr) {
-    if ((st = set_lds(&attn_fp8_fwd_kernel<true>, lds, granted[1])) != GPS_OK) return st;
+    if ((st = gps_dev::grant_lds((const void *)&attn_fp8_fwd_kernel<true>, lds, 160 * 1024, granted[1])) != GPS_OK) return st;
     hipLaunchKernelGGL((attn_fp8_fwd_kernel<true>), grid, block, lds, s, P);
   } else {
-    if ((st = set_lds(&attn_fp8_fwd_kernel<false>, lds, granted[0])) != GPS_OK) return st;
+    if ((st = gps_dev::grant_lds((const void *)&attn_fp8_fwd_kernel<false>, lds, 160 * 1024, granted[0])) != GPS_OK) return st;
     hipLaunchKernelGGL((attn_fp8_fwd_kernel<false>), grid, block, lds, s, P);
   }
   return hipGetLastError() == hipSuccess ? GPS_OK : GPS_ERR_LAUNCH;

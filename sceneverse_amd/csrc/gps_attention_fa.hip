@@ -24,24 +24,17 @@
 #include <stdlib.h>
 
 #include "gps_hip.h"
-#include "gps_attention_ex.h"
+#include "gps_attention_dev.h"
+#include "gps_attention_run.h"
+#include "gps_dropout.h"
 
 namespace gps_attn_fa {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
+using namespace gps_attn_dev;
+using namespace gps_dropout;
 
-constexpr int DH = 64;
-constexpr int KS = DH + 8;            // LDS row pitch (144 B)
 constexpr int BLK = 64;               // rows per streamed block, and queries / keys per workgroup
-constexpr int kThreads = 256;
-constexpr float kLog2e = 1.4426950408889634f;
-constexpr float kLn2 = 0.6931471805599453f;
-constexpr float kC = 0.125f * kLog2e;
+constexpr int kThreads = kStreamThreads;
 
 struct Params {
   int B, H, L, Lq;                    // L / Lq: capacities of keys / queries (pitch of lse, delta and of the dropout counter)
@@ -60,60 +53,6 @@ struct Params {
   const unsigned long long *seed_dev;
   const int *seq_order, *q_limit, *cu_rows;
 };
-
-__device__ __forceinline__ unsigned int pack2(float lo, float hi) {
-  const bf16x2_t h = {(__bf16)lo, (__bf16)hi};
-  return __builtin_bit_cast(unsigned int, h);
-}
-__device__ __forceinline__ bf16x8 as_frag(u32x4 v) { return __builtin_bit_cast(bf16x8, v); }
-__device__ __forceinline__ u32x4 zero4() { u32x4 z = {0u, 0u, 0u, 0u}; return z; }
-__device__ __forceinline__ f32x4 zero_acc() { f32x4 z = {0.f, 0.f, 0.f, 0.f}; return z; }
-__device__ __forceinline__ float bf2f(unsigned int bits16) { return __uint_as_float(bits16 << 16); }
-__device__ __forceinline__ f32x4 mfma32(bf16x8 a, bf16x8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ bf16x8 pack_tiles(const f32x4 &a, const f32x4 &b) {
-  const u32x4 v = {pack2(a[0], a[1]), pack2(a[2], a[3]), pack2(b[0], b[1]), pack2(b[2], b[3])};
-  return as_frag(v);
-}
-__device__ __forceinline__ float xor_max_g(float v) {
-  v = fmaxf(v, __shfl_xor(v, 16, 64));
-  return fmaxf(v, __shfl_xor(v, 32, 64));
-}
-__device__ __forceinline__ float xor_sum_g(float v) {
-  v += __shfl_xor(v, 16, 64);
-  return v + __shfl_xor(v, 32, 64);
-}
-// the dropout stream of gps_attention.hip's streaming kernels, bit for bit
-__device__ __forceinline__ unsigned int mix32(unsigned int x) {
-  x ^= x >> 16;
-  x *= 0x21F0AAADu;
-  x ^= x >> 15;
-  x *= 0x735A2D97u;
-  x ^= x >> 15;
-  return x;
-}
-__device__ __forceinline__ unsigned int seed_fold(unsigned long long seed) {
-  return mix32((unsigned int)seed ^ mix32((unsigned int)(seed >> 32) + 0x9E3779B9u));
-}
-__device__ __forceinline__ unsigned int pair_rng(unsigned int seedmix, unsigned int row_pair_base, int t) {
-  return mix32((row_pair_base + (unsigned int)(t >> 1)) ^ seedmix);
-}
-
-__device__ __forceinline__ u32x2 tr4(const uint16_t *tile, int row0, int col0, int lane) {
-  const int i = lane & 15;
-  const uint16_t *p = tile + (row0 + (i >> 2)) * KS + col0 + 4 * (i & 3);
-  const s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4 *)p);
-  return __builtin_bit_cast(u32x2, v);
-}
-// MFMA operand holding M[rows][col0 + (lane & 15)] for the rows 32 c + 4 g + 0..3, 32 c + 16 + 4 g + 0..3 of a row-major
-// [64][KS] block: the K order in which pack_tiles lays out the D fragments of two adjacent 16-row tiles
-__device__ __forceinline__ bf16x8 tr_frag_perm(const uint16_t *tile, int c, int col0, int lane) {
-  const int g = lane >> 4;
-  const u32x2 lo = tr4(tile, 32 * c + 4 * g, col0, lane), hi = tr4(tile, 32 * c + 16 + 4 * g, col0, lane);
-  const u32x4 v = {lo[0], lo[1], hi[0], hi[1]};
-  return as_frag(v);
-}
 
 // which (sequence, head, block) a workgroup owns: the blocks of one (sequence, head) -- which re-read the same K / V (or
 // Q / dO) rows -- sit on ONE XCD (block id mod 8) and share its L2
@@ -149,36 +88,6 @@ __device__ __forceinline__ bool locate(const Params &P, Work &W) {
     if (P.q_limit) W.Lq = min(W.Lq, max(P.q_limit[b], 0));    // only the leading queries are wanted
   }
   return true;
-}
-
-// one 64-row block of two bf16 matrices (head h's 64 columns; rows >= rows_valid zero) -> two LDS tiles [64][KS]:
-// issue() requests the four 16-byte pieces of a thread, commit() writes them
-struct BlockPair {
-  u32x4 va[2], vb[2];
-  __device__ __forceinline__ void issue(const uint16_t *src_a, int ld_a, const uint16_t *src_b, int ld_b, int row_first, int rows_valid) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int e = threadIdx.x + i * kThreads, r = row_first + (e >> 3), ch = e & 7;
-      va[i] = zero4();
-      vb[i] = zero4();
-      if (r < rows_valid) {
-        va[i] = *reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(src_a) + (unsigned int)(r * ld_a + ch * 8) * 2u);
-        vb[i] = *reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(src_b) + (unsigned int)(r * ld_b + ch * 8) * 2u);
-      }
-    }
-  }
-  __device__ __forceinline__ void commit(uint16_t *dst_a, uint16_t *dst_b) const {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int e = threadIdx.x + i * kThreads, r = e >> 3, ch = e & 7;
-      *reinterpret_cast<u32x4 *>(dst_a + r * KS + ch * 8) = va[i];
-      *reinterpret_cast<u32x4 *>(dst_b + r * KS + ch * 8) = vb[i];
-    }
-  }
-};
-
-__device__ __forceinline__ u32x4 load_frag(const uint16_t *base, int row, int ld, int col) {
-  return *reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(base) + (unsigned int)(row * ld + col) * 2u);
 }
 
 constexpr int kTile = BLK * KS;           // elements of one LDS tile
@@ -217,7 +126,7 @@ __global__ __launch_bounds__(kThreads) void fwd_kernel(const Params P) {
 
   const bool dropout = P.drop_thr != 0u;
   const float keep_scale = dropout ? 1.f / (1.f - P.p_drop) : 1.f;
-  const unsigned int seedmix = dropout ? seed_fold(P.seed + (P.seed_dev ? *P.seed_dev : 0ull)) : 0u;
+  const unsigned int seedmix = dropout ? seed_fold(effective_seed(P.seed, P.seed_dev)) : 0u;
   const unsigned int thr16 = P.drop_thr >> 16;
   const unsigned int rp = (((unsigned int)W.b * P.H + h) * P.Lq + qi) * (unsigned int)((P.L + 1) >> 1);
 
@@ -284,7 +193,7 @@ __global__ __launch_bounds__(kThreads) void fwd_kernel(const Params P) {
       for (int c = 0; c < 2; ++c) {
         const bf16x8 pb = pack_tiles(x[2 * c], x[2 * c + 1]);
 #pragma unroll
-        for (int n = 0; n < 4; ++n) o[n] = mfma32(tr_frag_perm(Vc, c, 16 * n, lane), pb, o[n]);
+        for (int n = 0; n < 4; ++n) o[n] = mfma32(tr_frag_perm(Vc, KS, c, 16 * n, lane), pb, o[n]);
       }
     }
     if (more) {
@@ -371,7 +280,7 @@ __global__ __launch_bounds__(kThreads) void bwd_dq_kernel(const Params P) {
 
   const bool dropout = P.drop_thr != 0u;
   const float keep_scale = dropout ? 1.f / (1.f - P.p_drop) : 1.f;
-  const unsigned int seedmix = dropout ? seed_fold(P.seed + (P.seed_dev ? *P.seed_dev : 0ull)) : 0u;
+  const unsigned int seedmix = dropout ? seed_fold(effective_seed(P.seed, P.seed_dev)) : 0u;
   const unsigned int thr16 = P.drop_thr >> 16;
   const unsigned int rp = (((unsigned int)W.b * P.H + h) * P.Lq + qi) * (unsigned int)((P.L + 1) >> 1);
 
@@ -420,7 +329,7 @@ __global__ __launch_bounds__(kThreads) void bwd_dq_kernel(const Params P) {
       for (int c = 0; c < 2; ++c) {
         const bf16x8 db = pack_tiles(ds[2 * c], ds[2 * c + 1]);
 #pragma unroll
-        for (int n = 0; n < 4; ++n) o[n] = mfma32(tr_frag_perm(Kc, c, 16 * n, lane), db, o[n]);
+        for (int n = 0; n < 4; ++n) o[n] = mfma32(tr_frag_perm(Kc, KS, c, 16 * n, lane), db, o[n]);
       }
     }
     if (more) {
@@ -492,7 +401,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(3, 3))
 
   const bool dropout = P.drop_thr != 0u;
   const float keep_scale = dropout ? 1.f / (1.f - P.p_drop) : 1.f;
-  const unsigned int seedmix = dropout ? seed_fold(P.seed + (P.seed_dev ? *P.seed_dev : 0ull)) : 0u;
+  const unsigned int seedmix = dropout ? seed_fold(effective_seed(P.seed, P.seed_dev)) : 0u;
   const unsigned int thr16 = P.drop_thr >> 16;
   const unsigned int pitch2 = (unsigned int)((P.L + 1) >> 1);
   const unsigned int bh_base = ((unsigned int)W.b * P.H + h) * P.Lq;
@@ -566,8 +475,8 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(3, 3))
         const bf16x8 db = pack_tiles(ds[0], ds[1]);
 #pragma unroll
         for (int n = 0; n < 4; ++n) {
-          dv[n] = mfma32(tr_frag_perm(Oc, c, 16 * n, lane), pb, dv[n]);
-          dk[n] = mfma32(tr_frag_perm(Qc, c, 16 * n, lane), db, dk[n]);
+          dv[n] = mfma32(tr_frag_perm(Oc, KS, c, 16 * n, lane), pb, dv[n]);
+          dk[n] = mfma32(tr_frag_perm(Qc, KS, c, 16 * n, lane), db, dk[n]);
         }
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -610,7 +519,7 @@ int run_plain_blocks(const gps_attn_args *a, bool backward, hipStream_t s) {
   P.q = (const uint16_t *)a->q; P.k = (const uint16_t *)a->k; P.v = (const uint16_t *)a->v;
   P.mask = a->mask; P.out = (uint16_t *)a->out; P.lse = a->lse;
   P.p_drop = a->p_drop; P.seed = a->seed; P.seed_dev = (const unsigned long long *)a->seed_dev;
-  P.drop_thr = a->p_drop > 0.f ? (unsigned int)((double)a->p_drop * 4294967296.0) : 0u;
+  P.drop_thr = gps_dropout::drop_threshold(a->p_drop);
   P.cu_rows = a->cu_rows;
   P.seq_order = a->cu_rows ? a->seq_order : nullptr;
   P.q_limit = a->cu_rows ? a->q_limit : nullptr;

@@ -1,5 +1,5 @@
-// Internal (not installed): functions shared by gps_attention.hip (bf16 kernels, argument checks) and
-// gps_attention_ex.hip (fp32-operand kernels, fp8-product forward kernel).
+// Internal (not installed): the run functions of the five attention files.  gps_attention.hip's run_ex checks the
+// arguments of the C entry points and dispatches to the others; each takes checked arguments and launches its family.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -31,31 +31,22 @@
 #include <stdlib.h>
 
 #include "gps_hip.h"
+#include "gps_attention_dev.h"
+#include "gps_attention_run.h"
 #include "gps_device_flags.h"
-#include "gps_attention_ex.h"
+#include "gps_dropout.h"
 
 namespace gps_attn_sp {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(4))) _Float16 f16x4;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
+using namespace gps_attn_dev;
+using namespace gps_dropout;
 
 // register budget of the forward kernel (waves per SIMD it is compiled for); the backward kernel takes it as a template argument
 #ifndef GPS_SP_FWD_OCC
 #define GPS_SP_FWD_OCC __attribute__((amdgpu_waves_per_eu(NT <= 5 ? 4 : 2, NT <= 5 ? 4 : 2)))
 #endif
 
-constexpr int DH = 64;
-constexpr int KS = DH + 8;                       // pitch of the row-major K / V / Q / dO tiles (144 B)
-constexpr float kLog2e = 1.4426950408889634f;
-constexpr float kLn2 = 0.6931471805599453f;
-constexpr float kC = 0.125f * kLog2e;            // base-2 logit per unit of q . k
 constexpr float kInvC = 8.f * kLn2;              // 1 / kC
-constexpr float kClamp2 = -19.931568569324174f;  // log2(1e-6)
 
 struct Params {
   int B, H, L, nt;
@@ -76,34 +67,9 @@ struct Params {
   const unsigned long long *seed_dev;
 };
 
-__device__ __forceinline__ unsigned int pack2(float lo, float hi) {     // v_cvt_pk_bf16_f32: round to nearest even
-  const bf16x2_t h = {(__bf16)lo, (__bf16)hi};
-  return __builtin_bit_cast(unsigned int, h);
-}
-__device__ __forceinline__ bf16x8 as_frag(u32x4 v) { return __builtin_bit_cast(bf16x8, v); }
-__device__ __forceinline__ u32x4 zero4() { u32x4 z = {0u, 0u, 0u, 0u}; return z; }
-__device__ __forceinline__ f32x4 zero_acc() { f32x4 z = {0.f, 0.f, 0.f, 0.f}; return z; }
-__device__ __forceinline__ float bf2f(unsigned int bits16) { return __uint_as_float(bits16 << 16); }
-
-__device__ __forceinline__ f32x4 mfma32(bf16x8 a, bf16x8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
 __device__ __forceinline__ f32x4 mfma16(u32x2 a, u32x2 b, f32x4 c) {   // 16-deep reduction: k = 4 g + 0..3 per lane
   return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(s16x4, a), __builtin_bit_cast(s16x4, b), c, 0, 0, 0);
 }
-
-__device__ __forceinline__ void block_to_bh(int B, int H, int &b, int &h) {
-  const int id = blockIdx.x;
-  if ((B & 7) == 0) {       // the 12 heads of a scene on one XCD (block id mod 8): they share its pairwise planes in that L2
-    const int xcd = id & 7, slot = id >> 3;
-    b = (slot / H) * 8 + xcd;
-    h = slot % H;
-  } else {
-    b = id / H;
-    h = id % H;
-  }
-}
-
 constexpr int kThreads = 320;                    // five waves: one query strip per wave up to 80 tokens, two up to 144
 
 // Two row-major tiles (head h's 64 columns of rows [0, R) of two bf16 matrices; rows >= rows_valid zero) -> LDS [R][KS], in
@@ -136,64 +102,13 @@ struct StagePair {
     }
   }
 };
-
-// hardware-transposed read: the 16-lane group of `lane` gets rows row0 .. row0 + 3 of columns col0 .. col0 + 15 of a
-// row-major bf16 tile, lane i (= lane & 15) receiving column col0 + i (4 values = 2 dwords)
-__device__ __forceinline__ u32x2 tr4(const uint16_t *tile, int pitch, int row0, int col0, int lane) {
-  const int i = lane & 15;
-  const uint16_t *p = tile + (row0 + (i >> 2)) * pitch + col0 + 4 * (i & 3);
-  const s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4 *)p);
-  return __builtin_bit_cast(u32x2, v);
-}
-// MFMA operand (A: row = lane & 15 of M^T; B: column = lane & 15 of M) holding M[rows][col0 + (lane & 15)] for the eight rows
-//   permuted:  32 c + 4 g + 0..3, 32 c + 16 + 4 g + 0..3   (the K order of pack_tiles: D fragments of two adjacent tiles)
-//   natural:   32 c + 8 g + 0..7
-__device__ __forceinline__ bf16x8 tr_frag_perm(const uint16_t *tile, int pitch, int c, int col0, int lane) {
-  const int g = lane >> 4;
-  const u32x2 lo = tr4(tile, pitch, 32 * c + 4 * g, col0, lane), hi = tr4(tile, pitch, 32 * c + 16 + 4 * g, col0, lane);
-  const u32x4 v = {lo[0], lo[1], hi[0], hi[1]};
-  return as_frag(v);
-}
-__device__ __forceinline__ bf16x8 tr_frag_nat(const uint16_t *tile, int pitch, int c, int col0, int lane) {
-  const int g = lane >> 4;
-  const u32x2 lo = tr4(tile, pitch, 32 * c + 8 * g, col0, lane), hi = tr4(tile, pitch, 32 * c + 8 * g + 4, col0, lane);
-  const u32x4 v = {lo[0], lo[1], hi[0], hi[1]};
-  return as_frag(v);
-}
-__device__ __forceinline__ bf16x8 pack_tiles(const f32x4 &a, const f32x4 &b) {
-  const u32x4 v = {pack2(a[0], a[1]), pack2(a[2], a[3]), pack2(b[0], b[1]), pack2(b[2], b[3])};
-  return as_frag(v);
-}
-__device__ __forceinline__ u32x2 pack_tile(const f32x4 &a) {
-  const u32x2 v = {pack2(a[0], a[1]), pack2(a[2], a[3])};
-  return v;
-}
-
-__device__ __forceinline__ float xor_max_g(float v) {   // across the 4 lane groups (same lane & 15)
-  v = fmaxf(v, __shfl_xor(v, 16, 64));
-  return fmaxf(v, __shfl_xor(v, 32, 64));
-}
-__device__ __forceinline__ float xor_sum_g(float v) {
-  v += __shfl_xor(v, 16, 64);
-  return v + __shfl_xor(v, 32, 64);
-}
-
 // what a query strip reads from global memory for the spatial term: the (pre-scaled) conditioning vector of the lane's
 // query and the fp16 planes of (query, keys 16 j + 4 g + 0..3) for every tile
 template <int NT>
 struct Spatial {
-  unsigned int wraw[3];   // (bias, w_1..w_5) as loaded: six bf16
+  unsigned int wraw[3];   // (bias, w_1..w_5) as loaded: six bf16; unpacked (cond_vector) where it is used, so that nothing waits on the load
   u32x2 pl[5][NT];        // 4 halves each
 };
-// -log2(e) * (bias, w_1..w_5); unpacked where it is used, so that nothing waits on the load at request time
-template <int NT>
-__device__ __forceinline__ void cond_vector(const Spatial<NT> &S, float (&w)[6]) {
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    w[2 * i] = -kLog2e * bf2f(S.wraw[i] & 0xFFFFu);
-    w[2 * i + 1] = -kLog2e * __uint_as_float(S.wraw[i] & 0xFFFF0000u);
-  }
-}
 // planes of tiles [J0, J1) of the lane's query row
 template <int NT, int J0, int J1>
 __device__ __forceinline__ void load_planes(const Params &P, int b, int qc, int g, Spatial<NT> &S) {
@@ -220,10 +135,6 @@ template <int NT>
 __device__ __forceinline__ void load_spatial(const Params &P, int b, int h, int qc, int g, Spatial<NT> &S) {
   load_cond<NT>(P, b, h, qc, S);
   load_planes<NT, 0, NT>(P, b, qc, g, S);
-}
-// one 16-byte fragment load: row `row` (pitch ld elements) of a bf16 matrix whose head block starts at `base` (uniform)
-__device__ __forceinline__ u32x4 load_frag(const uint16_t *base, int row, int ld, int col) {
-  return *reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(base) + (unsigned int)(row * ld + col) * 2u);
 }
 // u = -log2(e) z of (query, key 16 j + 4 g + r)
 template <int NT>
@@ -254,7 +165,7 @@ __device__ __forceinline__ void fwd_request(const Params &P, const uint16_t *qb,
 template <int NT>
 __device__ __forceinline__ void fwd_bias(FwdStrip<NT> &F) {
   float w[6];
-  cond_vector<NT>(F.S, w);
+  cond_vector(F.S.wraw, w);
 #pragma unroll
   for (int j = 0; j < NT; ++j)
 #pragma unroll
@@ -415,7 +326,7 @@ __device__ __forceinline__ void bwd_strip(const Params &P, const uint16_t *Ks, c
     __builtin_amdgcn_sched_barrier(0);            // one tile's fragments in flight, not all 4 NT of them (registers)
   }
   float w[6], dw[6];
-  cond_vector<NT>(F.S, w);
+  cond_vector(F.S.wraw, w);
   const float lse2 = F.lse2 * kLog2e;
   unsigned int gate2[NT][2];                       // the gate e / (1 + e) of the spatial gradient, bf16 pairs
   float delta = 0.f;
@@ -617,16 +528,11 @@ int launch(const Params &P, bool backward, hipStream_t s) {
   constexpr int kOccBig = NT <= 5 ? 4 : 2;
   const bool alt = backward && NT <= 5 && bwd_occ() == 3;
   // one flag per INSTANTIATION that can be launched below (forward | backward | backward at the alternative occupancy)
-  static gps_dev::PerDevice<bool, 3> granted_dev;
-  bool *granted = granted_dev.row();
-  const int which = !backward ? 0 : (alt ? 2 : 1);
-  if (lds > 64 * 1024 && !granted[which]) {
-    const void *fn = !backward ? (const void *)&fwd_kernel<NT>
-                     : alt     ? (const void *)&bwd_kernel<NT, (NT <= 5 ? 3 : kOccBig)>
-                               : (const void *)&bwd_kernel<NT, kOccBig>;
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return GPS_ERR_LAUNCH;
-    granted[which] = true;
-  }
+  static gps_dev::PerDevice<size_t, 3> granted_dev;
+  const void *fn = !backward ? (const void *)&fwd_kernel<NT>
+                   : alt     ? (const void *)&bwd_kernel<NT, (NT <= 5 ? 3 : kOccBig)>
+                             : (const void *)&bwd_kernel<NT, kOccBig>;
+  if (gps_dev::grant_lds(fn, lds, lds, granted_dev.row()[!backward ? 0 : (alt ? 2 : 1)]) != GPS_OK) return GPS_ERR_LAUNCH;
   if (!backward) hipLaunchKernelGGL((fwd_kernel<NT>), grid, block, lds, s, P);
   else if (alt) hipLaunchKernelGGL((bwd_kernel<NT, (NT <= 5 ? 3 : kOccBig)>), grid, block, lds, s, P);
   else hipLaunchKernelGGL((bwd_kernel<NT, kOccBig>), grid, block, lds, s, P);
@@ -638,23 +544,9 @@ int launch(const Params &P, bool backward, hipStream_t s) {
 // PLAIN form (no pairwise term) for short fixed-length rows -- the 130-token joint sequences of the unified encoder
 // (nn.MultiheadAttention with key_padding_mask and dropout on the probabilities, modules/layers/transformers.py:141):
 // the same single-sweep structure (K / V resident, one query strip per wave, P and dS parked in LDS, dK / dV as pure
-// MFMA), dropout from the streaming kernels' stream (one hash per (query, key pair): gps_attention.hip pair_rng), so a
+// MFMA), dropout from the streaming kernels' stream (one hash per (query, key pair): gps_dropout.h pair_rng), so a
 // forward of this family pairs with a backward of any other.
 // ==========================================================================================
-__device__ __forceinline__ unsigned int mix32(unsigned int x) {
-  x ^= x >> 16;
-  x *= 0x21F0AAADu;
-  x ^= x >> 15;
-  x *= 0x735A2D97u;
-  x ^= x >> 15;
-  return x;
-}
-__device__ __forceinline__ unsigned int seed_fold(unsigned long long seed) {
-  return mix32((unsigned int)seed ^ mix32((unsigned int)(seed >> 32) + 0x9E3779B9u));
-}
-__device__ __forceinline__ unsigned int pair_rng(unsigned int seedmix, unsigned int row_pair_base, int t) {
-  return mix32((row_pair_base + (unsigned int)(t >> 1)) ^ seedmix);
-}
 struct Drop {                 // dropout state of a query row
   bool on;
   float keep_scale;
@@ -662,7 +554,7 @@ struct Drop {                 // dropout state of a query row
   __device__ __forceinline__ void init(const Params &P, int b, int h, int qi) {
     on = P.drop_thr != 0u;
     keep_scale = on ? 1.f / (1.f - P.p_drop) : 1.f;
-    seedmix = on ? seed_fold(P.seed + (P.seed_dev ? *P.seed_dev : 0ull)) : 0u;
+    seedmix = on ? seed_fold(effective_seed(P.seed, P.seed_dev)) : 0u;
     thr16 = P.drop_thr >> 16;
     rp = (((unsigned int)b * P.H + h) * P.L + qi) * (unsigned int)((P.L + 1) >> 1);
   }
@@ -925,13 +817,9 @@ template <int NT>
 int launch_plain(const Params &P, bool backward, hipStream_t s) {
   const dim3 grid(P.B * P.H), block(64 * NT);
   const size_t lds = backward ? bwd_lds<NT>() : fwd_lds<NT>();
-  static gps_dev::PerDevice<bool, 2> granted_dev;
-  bool *granted = granted_dev.row();
-  if (lds > 64 * 1024 && !granted[backward ? 1 : 0]) {
-    const void *fn = backward ? (const void *)&pbwd_kernel<NT> : (const void *)&pfwd_kernel<NT>;
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return GPS_ERR_LAUNCH;
-    granted[backward ? 1 : 0] = true;
-  }
+  static gps_dev::PerDevice<size_t, 2> granted_dev;
+  const void *fn = backward ? (const void *)&pbwd_kernel<NT> : (const void *)&pfwd_kernel<NT>;
+  if (gps_dev::grant_lds(fn, lds, lds, granted_dev.row()[backward ? 1 : 0]) != GPS_OK) return GPS_ERR_LAUNCH;
   if (backward) hipLaunchKernelGGL((pbwd_kernel<NT>), grid, block, lds, s, P);
   else hipLaunchKernelGGL((pfwd_kernel<NT>), grid, block, lds, s, P);
   return hipGetLastError() == hipSuccess ? GPS_OK : GPS_ERR_LAUNCH;
@@ -976,7 +864,7 @@ int run_plain_resident(const gps_attn_args *a, bool backward, hipStream_t s) {
   P.q = (const uint16_t *)a->q; P.k = (const uint16_t *)a->k; P.v = (const uint16_t *)a->v;
   P.mask = a->mask; P.out = (uint16_t *)a->out; P.lse = a->lse;
   P.p_drop = a->p_drop; P.seed = a->seed; P.seed_dev = (const unsigned long long *)a->seed_dev;
-  P.drop_thr = a->p_drop > 0.f ? (unsigned int)((double)a->p_drop * 4294967296.0) : 0u;
+  P.drop_thr = gps_dropout::drop_threshold(a->p_drop);
   if (backward) {
     P.dout = (const uint16_t *)a->dout; P.dq = (uint16_t *)a->dq; P.dk = (uint16_t *)a->dk; P.dv = (uint16_t *)a->dv;
     P.ld_dqkv = a->ld_dq;

@@ -22,27 +22,16 @@
 #include <stdint.h>
 
 #include "gps_hip.h"
-#include "gps_attention_ex.h"
+#include "gps_attention_dev.h"
+#include "gps_attention_run.h"
 
 namespace gps_attn_spl {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(4))) _Float16 f16x4;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
+using namespace gps_attn_dev;
 
-constexpr int DH = 64;
-constexpr int KS = DH + 8;                       // pitch of the row-major Q / K / V / dO tiles (144 B)
 constexpr int BLK = 64;                          // rows per streamed block, and queries / keys per workgroup
-constexpr int kThreads = 256;
+constexpr int kThreads = kStreamThreads;
 constexpr int TPK = 16 + 8;                      // pitch of a wave's parked P / dS rows in the dK / dV launch (16 keys)
-constexpr float kLog2e = 1.4426950408889634f;
-constexpr float kLn2 = 0.6931471805599453f;
-constexpr float kC = 0.125f * kLog2e;            // base-2 logit per unit of q . k
-constexpr float kClamp2 = -19.931568569324174f;  // log2(1e-6)
 
 struct Params {
   int B, H, L, nblk;                             // nblk: 64-row blocks of the OWNED side per (scene, head)
@@ -58,60 +47,6 @@ struct Params {
   uint16_t *dsw;                                 // bf16, addressed like sw with ld_dsw
   float *delta;                                  // (B, H, L): written by launch 1, read by launch 2
 };
-
-__device__ __forceinline__ unsigned int pack2(float lo, float hi) {     // v_cvt_pk_bf16_f32: round to nearest even
-  const bf16x2_t h = {(__bf16)lo, (__bf16)hi};
-  return __builtin_bit_cast(unsigned int, h);
-}
-__device__ __forceinline__ bf16x8 as_frag(u32x4 v) { return __builtin_bit_cast(bf16x8, v); }
-__device__ __forceinline__ u32x4 zero4() { u32x4 z = {0u, 0u, 0u, 0u}; return z; }
-__device__ __forceinline__ f32x4 zero_acc() { f32x4 z = {0.f, 0.f, 0.f, 0.f}; return z; }
-__device__ __forceinline__ float bf2f(unsigned int bits16) { return __uint_as_float(bits16 << 16); }
-__device__ __forceinline__ f32x4 mfma32(bf16x8 a, bf16x8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ bf16x8 pack_tiles(const f32x4 &a, const f32x4 &b) {
-  const u32x4 v = {pack2(a[0], a[1]), pack2(a[2], a[3]), pack2(b[0], b[1]), pack2(b[2], b[3])};
-  return as_frag(v);
-}
-__device__ __forceinline__ u32x2 pack_tile(const f32x4 &a) {
-  const u32x2 v = {pack2(a[0], a[1]), pack2(a[2], a[3])};
-  return v;
-}
-__device__ __forceinline__ float xor_max_g(float v) {   // across the 4 lane groups (same lane & 15)
-  v = fmaxf(v, __shfl_xor(v, 16, 64));
-  return fmaxf(v, __shfl_xor(v, 32, 64));
-}
-__device__ __forceinline__ float xor_sum_g(float v) {
-  v += __shfl_xor(v, 16, 64);
-  return v + __shfl_xor(v, 32, 64);
-}
-// hardware-transposed read: the 16-lane group of `lane` gets rows row0 .. row0 + 3 of columns col0 .. col0 + 15 of a
-// row-major bf16 tile, lane i (= lane & 15) receiving column col0 + i (4 values = 2 dwords)
-__device__ __forceinline__ u32x2 tr4(const uint16_t *tile, int pitch, int row0, int col0, int lane) {
-  const int i = lane & 15;
-  const uint16_t *p = tile + (row0 + (i >> 2)) * pitch + col0 + 4 * (i & 3);
-  const s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4 *)p);
-  return __builtin_bit_cast(u32x2, v);
-}
-// MFMA operand holding M[rows][col0 + (lane & 15)] for the eight rows
-//   permuted:  32 c + 4 g + 0..3, 32 c + 16 + 4 g + 0..3   (the K order of pack_tiles: D fragments of two adjacent tiles)
-//   natural:   32 c + 8 g + 0..7
-__device__ __forceinline__ bf16x8 tr_frag_perm(const uint16_t *tile, int pitch, int c, int col0, int lane) {
-  const int g = lane >> 4;
-  const u32x2 lo = tr4(tile, pitch, 32 * c + 4 * g, col0, lane), hi = tr4(tile, pitch, 32 * c + 16 + 4 * g, col0, lane);
-  const u32x4 v = {lo[0], lo[1], hi[0], hi[1]};
-  return as_frag(v);
-}
-__device__ __forceinline__ bf16x8 tr_frag_nat(const uint16_t *tile, int pitch, int c, int col0, int lane) {
-  const int g = lane >> 4;
-  const u32x2 lo = tr4(tile, pitch, 32 * c + 8 * g, col0, lane), hi = tr4(tile, pitch, 32 * c + 8 * g + 4, col0, lane);
-  const u32x4 v = {lo[0], lo[1], hi[0], hi[1]};
-  return as_frag(v);
-}
-__device__ __forceinline__ u32x4 load_frag(const uint16_t *base, int row, int ld, int col) {
-  return *reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(base) + (unsigned int)(row * ld + col) * 2u);
-}
 
 // which (scene, head, block) a workgroup owns: with B a multiple of 8 every workgroup of scene b runs on XCD b mod 8
 // (block id mod 8), so the heads and blocks of a scene -- which all read its pairwise planes -- share that L2
@@ -135,32 +70,6 @@ __device__ __forceinline__ void locate(const Params &P, Work &W) {
   W.blk = rem % P.nblk;
   W.row0 = (size_t)b * P.L;
 }
-
-// one 64-row block of two bf16 matrices (head h's 64 columns; rows >= rows_valid zero) -> two LDS tiles [64][KS]:
-// issue() requests the four 16-byte pieces of a thread, commit() writes them
-struct BlockPair {
-  u32x4 va[2], vb[2];
-  __device__ __forceinline__ void issue(const uint16_t *src_a, int ld_a, const uint16_t *src_b, int ld_b, int row_first, int rows_valid) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int e = threadIdx.x + i * kThreads, r = row_first + (e >> 3), ch = e & 7;
-      va[i] = zero4();
-      vb[i] = zero4();
-      if (r < rows_valid) {
-        va[i] = *reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(src_a) + (unsigned int)(r * ld_a + ch * 8) * 2u);
-        vb[i] = *reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(src_b) + (unsigned int)(r * ld_b + ch * 8) * 2u);
-      }
-    }
-  }
-  __device__ __forceinline__ void commit(uint16_t *dst_a, uint16_t *dst_b) const {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int e = threadIdx.x + i * kThreads, r = e >> 3, ch = e & 7;
-      *reinterpret_cast<u32x4 *>(dst_a + r * KS + ch * 8) = va[i];
-      *reinterpret_cast<u32x4 *>(dst_b + r * KS + ch * 8) = vb[i];
-    }
-  }
-};
 
 // additive key term (base 2): 0, or -inf for padded keys and keys past L
 __device__ __forceinline__ float key_term(const Params &P, size_t row0, int t) {
@@ -186,14 +95,6 @@ __device__ __forceinline__ void load_cond(const Params &P, size_t row0, int h, i
 #pragma unroll
   for (int i = 0; i < 3; ++i) raw[i] = p[i];
 }
-// -log2(e) * (bias, w_1..w_5)
-__device__ __forceinline__ void cond_vector(const unsigned int (&raw)[3], float (&w)[6]) {
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    w[2 * i] = -kLog2e * bf2f(raw[i] & 0xFFFFu);
-    w[2 * i + 1] = -kLog2e * __uint_as_float(raw[i] & 0xFFFF0000u);
-  }
-}
 // u = -log2(e) z of (query, key t0 + r);  e = 2^u,  log2(clamp(sigmoid z, 1e-6)) = max(-log2(1 + e), log2(1e-6))
 __device__ __forceinline__ float spatial_u(const Planes4 &S, const float (&w)[6], int r) {
   float u = w[0];
@@ -201,7 +102,6 @@ __device__ __forceinline__ float spatial_u(const Planes4 &S, const float (&w)[6]
   for (int d = 0; d < 5; ++d) u = fmaf((float)__builtin_bit_cast(f16x4, S.d[d])[r], w[1 + d], u);
   return u;
 }
-__device__ __forceinline__ float spatial_bias2(float e) { return fmaxf(-__builtin_amdgcn_logf(1.f + e), kClamp2); }
 
 constexpr int kTile = BLK * KS;                                              // elements of one LDS tile
 constexpr size_t kLdsQ = (size_t)4 * kTile * 2 + 2 * BLK * 4;                // K, V double-buffered + key terms

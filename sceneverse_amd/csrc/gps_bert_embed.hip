@@ -14,30 +14,21 @@
 //             gps_embedding_grad) + per-workgroup partial column sums for dgamma / dbeta (summed by
 //             gps_ln_reduce_partials); rows past the device-side row count get dz = 0.
 // The type-row gradient is the column sum of the position-table gradient (every row has exactly one position).
-// Dropout: the counter-based stream of gps_layernorm.hip (element index = row * d + column), recomputed in backward.
+// Dropout: the counter-based element stream of gps_dropout.h (element index = row * d + column), recomputed in backward.
 // HBM-bound: forward reads 3 KB (word row) and writes 4.5 KB per live row at d = 768; backward reads 6 KB, writes 3 KB.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "gps_hip.h"
+#include "gps_dropout.h"
 
 namespace gps_bert_embed {
+
+using namespace gps_dropout;
 
 constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / 64;
 
-__device__ __forceinline__ unsigned int mix32(unsigned int x) {      // as in gps_layernorm.hip
-  x ^= x >> 16;
-  x *= 0x21F0AAADu;
-  x ^= x >> 15;
-  x *= 0x735A2D97u;
-  x ^= x >> 15;
-  return x;
-}
-__device__ __forceinline__ unsigned int rng_u32(unsigned long long seed, unsigned long long idx) {
-  const unsigned int s = mix32((unsigned int)seed ^ mix32((unsigned int)(seed >> 32) + 0x9E3779B9u));
-  return mix32(((unsigned int)idx + (unsigned int)(idx >> 32) * 0x85EBCA6Bu) ^ s);
-}
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
@@ -639,7 +630,7 @@ int gps_bert_embed_forward(int n_rows, int d, const long long *ids, const long l
   const uintptr_t align = (uintptr_t)word | (uintptr_t)pos_table | (uintptr_t)type_row | (uintptr_t)gamma | (uintptr_t)beta |
                           (uintptr_t)y | (uintptr_t)y_bf16;
   if (align & 15) return GPS_ERR_UNSUPPORTED;
-  const unsigned int thr = p_drop > 0.f ? (unsigned int)((double)p_drop * 4294967296.0) : 0u;
+  const unsigned int thr = gps_dropout::drop_threshold(p_drop);
   const dim3 grid(grid_rows(n_rows)), block(kBlock);
   hipStream_t s = (hipStream_t)stream;
 #define GPS_BE_FWD(IT)                                                                                                     \
@@ -688,7 +679,7 @@ int gps_bert_embed_backward(int n_rows, int d, const float *dy, const void *dy_b
   const uintptr_t align = (uintptr_t)word | (uintptr_t)pos_table | (uintptr_t)type_row | (uintptr_t)gamma | (uintptr_t)dy |
                           (uintptr_t)dy_bf16 | (uintptr_t)dz;
   if (align & 15) return GPS_ERR_UNSUPPORTED;
-  const unsigned int thr = p_drop > 0.f ? (unsigned int)((double)p_drop * 4294967296.0) : 0u;
+  const unsigned int thr = gps_dropout::drop_threshold(p_drop);
   const dim3 grid(grid_rows(n_rows)), block(kBlock);
   const size_t lds = sizeof(float) * kWaves * d;
   hipStream_t s = (hipStream_t)stream;

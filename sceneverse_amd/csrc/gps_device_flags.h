@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <cstddef>
 
+#include "gps_hip.h"
+
 namespace gps_dev {
 
 constexpr int kMaxDevices = 32;
@@ -21,5 +23,16 @@ struct PerDevice {
   T v[kMaxDevices][N] = {};
   T *row() { return v[current_device()]; }
 };
+
+// Opt a kernel into more than 64 KiB of dynamic LDS before a launch that wants `lds` bytes: unless this device's last
+// grant for the kernel (`granted`, a PerDevice word of the call site) already covers it, ask for `ask` bytes (>= lds: the
+// call site's policy, exactly `lds` or the 160 KiB of a CU) and record them.
+inline int grant_lds(const void *kernel, size_t lds, size_t ask, size_t &granted) {
+  if (lds > 64 * 1024 && lds > granted) {
+    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ask) != hipSuccess) return GPS_ERR_LAUNCH;
+    granted = ask;
+  }
+  return GPS_OK;
+}
 
 }  // namespace gps_dev

@@ -27,6 +27,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "gps_dropout.h"
 #include "gps_gemm_layout.h"
 #include "gps_hip.h"
 
@@ -39,6 +40,7 @@ namespace gps { const int *object_extent(); }   // gps_point_ops.hip
 namespace gps_gemm {
 
 using namespace gps_gemm_layout;
+using namespace gps_dropout;
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
@@ -164,22 +166,6 @@ typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 __device__ __forceinline__ u32x2 pack4(const f32x4 &v) {     // v_cvt_pk_bf16_f32: round to nearest even
   const bf16x4 h = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
   return __builtin_bit_cast(u32x2, h);
-}
-// counter-based dropout RNG shared with gps_layernorm.hip / gps_attention.hip (splitmix64 finaliser)
-__device__ __forceinline__ unsigned int mix32(unsigned int x) {      // 32-bit avalanche hash ("lowbias32" constants)
-  x ^= x >> 16;
-  x *= 0x21F0AAADu;
-  x ^= x >> 15;
-  x *= 0x735A2D97u;
-  x ^= x >> 15;
-  return x;
-}
-// counter-based dropout stream: forward and backward draw the same bits for the same (seed, element index); the seed
-// part is wave-uniform (scalar unit), the element part costs 2 multiplies and 3 xor-shifts (the 64-bit splitmix of
-// the first version: ~30 vector instructions per element)
-__device__ __forceinline__ unsigned int rng_u32(unsigned long long seed, unsigned long long idx) {
-  const unsigned int s = mix32((unsigned int)seed ^ mix32((unsigned int)(seed >> 32) + 0x9E3779B9u));
-  return mix32(((unsigned int)idx + (unsigned int)(idx >> 32) * 0x85EBCA6Bu) ^ s);
 }
 // erf GELU (the reference's F.gelu / HF "gelu") and its derivative.  erf through Abramowitz-Stegun 7.1.26
 // (|error| <= 1.5e-7, far below the bf16 rounding of the result) so that the epilogue costs ~15 VALU per element
@@ -2465,7 +2451,7 @@ static int gps_gemm_fill_params(const gps_gemm_args *a, gps_gemm::Params &P, boo
   P.splits = P.kt_per_split > 0 ? (P.nkt + P.kt_per_split - 1) / P.kt_per_split : 1;   // no empty split
   if (P.splits < 1) P.splits = 1;
   P.keep_scale = a->p_drop > 0.f ? 1.f / (1.f - a->p_drop) : 1.f;
-  P.drop_thr = a->p_drop > 0.f ? (unsigned int)((double)a->p_drop * 4294967296.0) : 0u;
+  P.drop_thr = gps_dropout::drop_threshold(a->p_drop);
   P.seed = a->seed; P.seed_dev = (const unsigned long long *)a->seed_dev;
   P.extent_dev = a->extent_dev;
   P.row0 = a->form != GPS_GEMM_TN ? a->reserved2 : 0;

@@ -18,28 +18,16 @@
 #include <stdint.h>
 
 #include "gps_hip.h"
+#include "gps_dropout.h"
 
 namespace gps_ln {
+
+using namespace gps_dropout;
 
 constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / 64;
 constexpr int kMaxIter = 8;          // D <= 8 * 256 (ITERS = D / 256 is a template parameter)
 
-__device__ __forceinline__ unsigned int mix32(unsigned int x) {      // 32-bit avalanche hash ("lowbias32" constants)
-  x ^= x >> 16;
-  x *= 0x21F0AAADu;
-  x ^= x >> 15;
-  x *= 0x735A2D97u;
-  x ^= x >> 15;
-  return x;
-}
-// counter-based dropout stream: forward and backward draw the same bits for the same (seed, element index); the seed
-// part is wave-uniform (scalar unit), the element part costs 2 multiplies and 3 xor-shifts (the 64-bit splitmix of
-// the first version: ~30 vector instructions per element)
-__device__ __forceinline__ unsigned int rng_u32(unsigned long long seed, unsigned long long idx) {
-  const unsigned int s = mix32((unsigned int)seed ^ mix32((unsigned int)(seed >> 32) + 0x9E3779B9u));
-  return mix32(((unsigned int)idx + (unsigned int)(idx >> 32) * 0x85EBCA6Bu) ^ s);
-}
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
@@ -595,7 +583,7 @@ int gps_add_dropout_layernorm_forward_post(int n_rows, int d, int x_bf16, int h_
   if ((d & 255) || d > 256 * gps_ln::kMaxIter || ((d >> 8) > 4 && (d >> 8) != 8)) return GPS_ERR_UNSUPPORTED;
   if (n_rows == 0) return GPS_OK;
   if (!x || !h || !gamma || !beta || !y || !mean || !rstd) return GPS_ERR_INVALID_ARGUMENT;
-  const unsigned int thr = p_drop > 0.f ? (unsigned int)((double)p_drop * 4294967296.0) : 0u;
+  const unsigned int thr = gps_dropout::drop_threshold(p_drop);
   const dim3 grid(gps_ln::grid_rows(n_rows)), block(gps_ln::kBlock);
   hipStream_t s = (hipStream_t)stream;
   const unsigned long long *sd = (const unsigned long long *)seed_dev;
@@ -662,7 +650,7 @@ int gps_add_dropout_layernorm_backward_post_acc(int n_rows, int d, int x_bf16, i
   if (n_rows == 0) return GPS_OK;
   if (!dy || !x || !h || !gamma || !mean || !rstd || !dx || !dh || !dgamma_part || !dbeta_part)
     return GPS_ERR_INVALID_ARGUMENT;
-  const unsigned int thr = p_drop > 0.f ? (unsigned int)((double)p_drop * 4294967296.0) : 0u;
+  const unsigned int thr = gps_dropout::drop_threshold(p_drop);
   const dim3 grid(gps_ln::grid_rows(n_rows)), block(gps_ln::kBlock);
   const size_t lds = sizeof(float) * gps_ln::kWaves * d;
   hipStream_t s = (hipStream_t)stream;

@@ -110,3 +110,27 @@ def test_gemm_epilogues_have_no_ieee_division_sequences():
     the GELU epilogue's vector instructions before round 4 replaced them by one v_rcp_f32."""
     text = _asm("gps_gemm")
     assert "v_div_scale_f32" not in text
+
+
+def test_digest_is_reproducible_and_ignores_comments():
+    """tools/asm_audit.py --digest: per kernel, a hash of the instructions and one of the .amdhsa_kernel descriptor.  Two
+    compilations of a file agree, and so does a copy of the file with a comment line added (the `__hip_cuid_*` symbol,
+    a hash of the source text, changes and must not count): the table moves only when the device code does."""
+    import asm_audit
+    src = os.path.join(ROOT, "sceneverse_amd", "csrc", "gps_embedding.hip")
+    with tempfile.TemporaryDirectory() as tmp:
+        first = asm_audit.digest(src, tmp)
+        again = asm_audit.digest(src, tmp)
+        copy_dir = os.path.join(tmp, "copy")
+        os.mkdir(copy_dir)
+        copy = os.path.join(copy_dir, "gps_embedding.hip")
+        with open(src) as fh, open(copy, "w") as out:
+            out.write("// a comment line that is not in the original\n" + fh.read())
+        commented = asm_audit.digest(copy, tmp)
+    names = [r[0] for r in first]
+    assert any("sum_kernel" in n for n in names) and any("mark_kernel" in n for n in names) and names == sorted(names)
+    for _, body, desc in first:
+        assert len(body) == 64 and len(desc) == 64 and body != desc
+    assert len({body for _, body, _ in first}) == len(first)       # different kernels, different instruction hashes
+    assert first == again
+    assert first == commented

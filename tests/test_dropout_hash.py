@@ -1,5 +1,6 @@
 """Statistical sanity of the counter-based dropout stream of the attention / LayerNorm / GEMM kernels
-(gps_attention.hip `mix32` / `pair_rng`, same function in gps_layernorm.hip and gps_gemm.hip), emulated in numpy:
+(sceneverse_amd/csrc/gps_dropout.h: `mix32`, `seed_fold`, `pair_rng`, the one definition every kernel file includes),
+emulated in numpy:
 keep rate = 1 - p, the two 16-bit halves of a pair hash independent, neighbouring indices and neighbouring seeds
 uncorrelated.  The kernels' own tests check that forward and backward draw the same mask; this one checks that the
 mask is a fair coin."""
