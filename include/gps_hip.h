@@ -394,6 +394,20 @@ GPS_API int gps_text_obj_ce_backward(int B, int O, int D, const float *obj, cons
                                      float eps, long long ignore_index, const float *cosv, const float *prob,
                                      const float *inv_o, const float *inv_t, const float *scal, const float *grad_out,
                                      float *dobj, float *dtext, gps_stream_t stream);
+/* TextObjWithinBatch, the BCE branch of task ScanQA (:29-35: F.normalize both sides, einsum('bod,bd->bo'),
+ * binary_cross_entropy_with_logits(reduction="sum", weight=masks) / B).  The same launches as the cross-entropy form up
+ * to the logits (same eps / clamp semantics, same D and O limits, same ticket contract); labels (B, O) int64 multi-hot,
+ * read in place; masks (B, O) bytes = the weight.  forward: cosv / inv_o (B, O), inv_t (B), coef (B, O) = mask (sigmoid(cosv)
+ * - label) (the logit gradients, read by the backward pass in place of the labels), loss_rows (B) scratch, scal[0] = the
+ * loss, scal[1] = B.  backward: dobj (B, O, D) and / or dtext (B, D) (either may be NULL). */
+GPS_API int gps_text_obj_bce_forward(int B, int O, int D, const float *obj, const float *text, const long long *labels,
+                                     const unsigned char *masks, float eps, float *cosv, float *coef, float *inv_o,
+                                     float *inv_t, float *loss_rows, float *scal, unsigned int *ticket,
+                                     gps_stream_t stream);
+GPS_API int gps_text_obj_bce_backward(int B, int O, int D, const float *obj, const float *text, float eps,
+                                      const float *cosv, const float *coef, const float *inv_o, const float *inv_t,
+                                      const float *scal, const float *grad_out, float *dobj, float *dtext,
+                                      gps_stream_t stream);
 /* _symmetric_clip_loss (:11-17) with the F.normalize of its two inputs (:60, :82-83; normalize = 0: rows taken as they
  * are) and s = min(*scale, max_scale) (the clamp of :57, :79).  a, b (n, D).  forward: M (n, n) = a_n b_n^T, lse_row /
  * lse_col / inv_a / inv_b / loss_rows (n), loss[0].  backward: da, db (n, D) (both or neither), dscale[0] (0 when the
@@ -405,6 +419,46 @@ GPS_API int gps_clip_loss_backward(int n, int D, int normalize, const float *a, 
                                    float max_scale, float eps, const float *M, const float *lse_row, const float *lse_col,
                                    const float *inv_a, const float *inv_b, const float *grad_out, float *da, float *db,
                                    float *dscale, float *ds_rows, unsigned int *ticket, gps_stream_t stream);
+
+/* ---- question answering: attention-flatten pooling and the multi-label answer loss -------------------------------------
+ * AttFlat (modules/heads/qa_head.py:56-67) after its first Linear + GELU: replaces mlp.linear (M -> G), masked_fill(-1e9),
+ * softmax(dim=1), the G weighted sums (:63-66) and the cat (:67).
+ *   x (B, T, D) bf16 (x_bf16 != 0) or fp32, row pitch ld_x elements (row (b, t) at (b T + t) ld_x);  h (B, T, M) bf16
+ *   (h_bf16 != 0) or fp32, contiguous;  w2 (G, M), b2 (G) fp32;  keep (B, T) bytes, 1 = valid token, NULL = all valid.
+ *   logit[b][t][g] = <h[b][t], w2[g]> + b2[g], replaced by -1e9f (fp32, the reference's literal, not -inf: a row with no
+ *   valid token gets the uniform 1 / T) where keep == 0;  att = softmax over t;
+ *   pooled[b][g D + d] = sum_t att[b][t][g] x[b][t][d]  (glimpse-major like the cat);  pooled (B, G D), att (B, T, G) fp32.
+ * Shapes served: 1 <= T <= 512, 1 <= G <= 4, D and M multiples of 8 with D <= 2048, M <= 1024, pitches multiples of 8,
+ * 16-byte aligned x / h / dx / dh / dpooled, B <= 65535; anything else GPS_ERR_UNSUPPORTED.  B = 0 returns GPS_OK.
+ * backward, from dpooled (B, G D) fp32: dx (x's dtype, pitch ld_dx; the gradient through the pooling only: the caller adds
+ * the path through h) and dh (h's dtype) -- either may be NULL --, dw2 (G, M), db2 (G) fp32.  keep == 0 positions pass no
+ * gradient to their logit (masked_fill).  workspace: gps_attflat_backward_ws_floats(B, T, G, M) floats; ticket: one
+ * unsigned int per call site, ZERO before the first launch and left zero.  dw2 / db2 are sums of per-workgroup partials
+ * added in a fixed order by the last workgroup to arrive: no float atomics, run-to-run identical. */
+GPS_API long long gps_attflat_backward_ws_floats(int B, int T, int G, int M);
+GPS_API int gps_attflat_forward(int B, int T, int G, int D, int M, int x_bf16, const void *x, long long ld_x, int h_bf16,
+                                const void *h, const float *w2, const float *b2, const unsigned char *keep,
+                                float *pooled, float *att, gps_stream_t stream);
+GPS_API int gps_attflat_backward(int B, int T, int G, int D, int M, int x_bf16, const void *x, long long ld_x, int h_bf16,
+                                 const void *h, const float *w2, const unsigned char *keep, const float *att,
+                                 const float *dpooled, void *dx, long long ld_dx, void *dh, float *dw2, float *db2,
+                                 float *workspace, unsigned int *ticket, gps_stream_t stream);
+/* loss[0] = scale * sum_{r,c} w[r][c] * BCEWithLogits(x[r][c], y[r][c]) in the stable form max(x, 0) - x y +
+ * log1p(exp(-|x|)): replaces answer_loss (optim/loss/loss.py:50-53: the .float() cast of the int64 labels and
+ * binary_cross_entropy_with_logits(reduction='sum') / B; scale = 1 / B) and serves og3d_multi_loss / txt_cls_multi_loss
+ * (:12-23) alike.  x (rows, cols) bf16 (x_bf16 != 0) or fp32, row pitch ld_x;  y (rows, cols) contiguous, int64 or fp32
+ * (y_f32 != 0), read in place;  w (rows, cols) bytes (0 = weight 0, else 1) or NULL.  Columns, pitches multiples of 8 and
+ * 16-byte aligned bases take 16-byte accesses, any other layout element accesses.  partial:
+ * gps_bce_logits_partial_floats(rows, cols) floats of scratch; ticket as above.  Workgroup partials over a fixed
+ * assignment of the elements, added in order by the last workgroup to arrive: run-to-run identical.  rows or cols == 0:
+ * GPS_OK, nothing written.  backward: dx = *grad_out * scale * w * (sigmoid(x) - y) in x's dtype, pitch ld_dx. */
+GPS_API int gps_bce_logits_partial_floats(int rows, int cols);
+GPS_API int gps_bce_logits_forward(int rows, int cols, int x_bf16, const void *x, long long ld_x, int y_f32,
+                                   const void *y, const unsigned char *w, float scale, float *partial, float *loss,
+                                   unsigned int *ticket, gps_stream_t stream);
+GPS_API int gps_bce_logits_backward(int rows, int cols, int x_bf16, const void *x, long long ld_x, int y_f32,
+                                    const void *y, const unsigned char *w, float scale, const float *grad_out, void *dx,
+                                    long long ld_dx, gps_stream_t stream);
 
 /* ---- y = x / max(||x||_2, eps) per row and its backward ------------------------------------------------------------
  * Replaces F.normalize(x, dim=-1, p=2) in the contrastive losses (optim/loss/contra_loss.py:38-39, 60, 82-83): torch runs

@@ -76,7 +76,8 @@ EPI_RELU_SPLIT, EPI_RELU_MAX16 = 6, 7
 EPI_BIAS_GELU_FACTOR, EPI_MUL_AUX = 8, 9
 
 # entries of SIGNATURES whose return value is not an `int` status
-NON_STATUS_RESTYPES = {"gps_embedding_grad_scratch_ints": ctypes.c_longlong, "gps_point_set_object_extent": None}
+NON_STATUS_RESTYPES = {"gps_embedding_grad_scratch_ints": ctypes.c_longlong, "gps_point_set_object_extent": None,
+                       "gps_attflat_backward_ws_floats": ctypes.c_longlong}
 
 # name -> argtypes, mirroring include/gps_hip.h one to one
 SIGNATURES = {
@@ -139,6 +140,14 @@ SIGNATURES = {
     "gps_text_obj_ce_forward": [_i, _i, _i, _vp, _vp, _vp, _vp, _f, ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "gps_text_obj_ce_backward": [_i, _i, _i, _vp, _vp, _vp, _f, ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                  _vp],
+    "gps_text_obj_bce_forward": [_i, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "gps_text_obj_bce_backward": [_i, _i, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "gps_attflat_backward_ws_floats": [_i, _i, _i, _i],
+    "gps_attflat_forward": [_i] * 6 + [_vp, ctypes.c_longlong, _i] + [_vp] * 7,
+    "gps_attflat_backward": [_i] * 6 + [_vp, ctypes.c_longlong, _i] + [_vp] * 5 + [_vp, ctypes.c_longlong] + [_vp] * 6,
+    "gps_bce_logits_partial_floats": [_i, _i],
+    "gps_bce_logits_forward": [_i, _i, _i, _vp, ctypes.c_longlong, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp],
+    "gps_bce_logits_backward": [_i, _i, _i, _vp, ctypes.c_longlong, _i, _vp, _vp, _f, _vp, _vp, ctypes.c_longlong, _vp],
     "gps_clip_loss_forward": [_i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "gps_clip_loss_backward": [_i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                _vp],

@@ -22,6 +22,7 @@ SOURCES = [
     ("gps_attention_fa.hip", []),
     ("gps_losses.hip", []),
     ("gps_contrastive.hip", []),
+    ("gps_qa.hip", []),
     ("gps_layernorm.hip", []),
     ("gps_objects.hip", []),
     ("gps_reduce.hip", []),

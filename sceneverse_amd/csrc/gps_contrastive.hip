@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gps_bce_dev.h"
 #include "gps_hip.h"
 
 namespace gps_contra {
@@ -72,8 +73,11 @@ __device__ __forceinline__ float peek(const float *p) { return __hip_atomic_load
 // TextObjWithinBatch.  One workgroup per scene b.
 //   cosv[b][o] = <obj_n[b][o], text_n[b]>     prob[b][o] = softmax over the unmasked objects    inv_o, inv_t: 1 / max(norm, eps)
 //   loss = mean over the scenes whose label != ignore_index of (lse_b - cosv[b][label_b])       scal[0] = loss, scal[1] = count
+// BCE (the branch of task ScanQA, contra_loss.py:29-35): labels (B, O) multi-hot, the masks are the weight;
+//   loss = sum_bo mask BCEWithLogits(cosv, label) / B,  prob[b][o] = mask (sigmoid(cosv) - label)  (the logit gradients),
+//   scal[1] = B.  Everything up to the logits is the same code.
 // ---------------------------------------------------------------------------------------------------------------------
-template <int NW>
+template <int NW, bool BCE>
 __global__ __launch_bounds__(64 * NW) void text_obj_fwd_kernel(int B, int O, int D, const float *__restrict__ obj,
                                                                const float *__restrict__ text,
                                                                const int64_t *__restrict__ labels,
@@ -132,6 +136,30 @@ __global__ __launch_bounds__(64 * NW) void text_obj_fwd_kernel(int B, int O, int
   __syncthreads();
   if (w != 0) return;
   const uint8_t *mk = masks + (size_t)b * O;
+  if constexpr (BCE) {
+    const int64_t *yb = labels + (size_t)b * O;
+    float s = 0.f;
+    for (int o = lane; o < O; o += 64) {
+      const float y = (float)yb[o], wk = mk[o] ? 1.f : 0.f;
+      s += wk * gps_bce::bce_term(lg[o], y);
+      prob[(size_t)b * O + o] = wk * (gps_bce::sigmoidf(lg[o]) - y);
+    }
+    s = wave_sum(s);
+    int last = 0;
+    if (lane == 0) {
+      inv_t[b] = it;
+      last = publish_and_last(loss_rows, b, s, ticket, B) ? 1 : 0;
+    }
+    if (!__shfl(last, 0, 64)) return;
+    float total = 0.f;
+    for (int i = lane; i < B; i += 64) total += peek(loss_rows + i);
+    total = wave_sum(total);
+    if (lane == 0) {
+      scal[0] = total / (float)B;
+      scal[1] = (float)B;
+    }
+    return;
+  }
   float m = -INFINITY;
   for (int o = lane; o < O; o += 64) m = fmaxf(m, mk[o] ? lg[o] : -INFINITY);
   m = wave_max(m);
@@ -171,6 +199,8 @@ __global__ __launch_bounds__(64 * NW) void text_obj_fwd_kernel(int B, int O, int
 // (4 per wave); blockIdx.x == G -> gradient of the scene's text row (sequential over the objects: fixed order).
 //   c_o = (prob_o - [o == label]) g / count;  dobj_o = inv_o c_o (text_n - obj_n_o cos_o);
 //   dtext = inv_t (sum_o c_o obj_n_o - text_n sum_o c_o cos_o)
+// BCE: c_o = prob_o g / B (prob = the logit gradients saved by the forward pass; labels are not read)
+template <bool BCE>
 __global__ __launch_bounds__(kBlock) void text_obj_bwd_kernel(int B, int O, int D, int G, const float *__restrict__ obj,
                                                                const float *__restrict__ text,
                                                                const int64_t *__restrict__ labels, float eps,
@@ -191,8 +221,8 @@ __global__ __launch_bounds__(kBlock) void text_obj_bwd_kernel(int B, int O, int 
     v.x *= it; v.y *= it; v.z *= it; v.w *= it;
     tn4[i] = v;
   }
-  const long long lab = labels[b];
-  const bool counted = lab != ignore_index && lab >= 0 && lab < O;
+  const long long lab = BCE ? -1 : labels[b];                       // BCE: no one-hot term, every scene counts
+  const bool counted = BCE || (lab != ignore_index && lab >= 0 && lab < O);
   const float gs = counted ? gout[0] / scal[1] : 0.f;
   const float *pb = prob + (size_t)b * O, *cb = cosv + (size_t)b * O, *ib = inv_o + (size_t)b * O;
   if ((int)blockIdx.x < G) {
@@ -440,7 +470,7 @@ int gps_text_obj_ce_forward(int B, int O, int D, const float *obj, const float *
   if ((D & 3) || D > 8192 || O > 4096 || !aligned16(obj) || !aligned16(text)) return GPS_ERR_UNSUPPORTED;
   const size_t lds = (size_t)(D + O + gps_contra::kFwdWaves) * sizeof(float);
   if (lds > 64 * 1024) return GPS_ERR_UNSUPPORTED;      // (no MaxDynamicSharedMemorySize grant: the default limit; callers fall back)
-  hipLaunchKernelGGL(gps_contra::text_obj_fwd_kernel<gps_contra::kFwdWaves>, dim3(B), dim3(64 * gps_contra::kFwdWaves), lds, (hipStream_t)stream, B, O, D,
+  hipLaunchKernelGGL((gps_contra::text_obj_fwd_kernel<gps_contra::kFwdWaves, false>), dim3(B), dim3(64 * gps_contra::kFwdWaves), lds, (hipStream_t)stream, B, O, D,
                      obj, text, (const int64_t *)labels, masks, eps, ignore_index, cosv, prob, inv_o, inv_t, loss_rows, scal,
                      ticket);
   return launch_status();
@@ -459,8 +489,42 @@ int gps_text_obj_ce_backward(int B, int O, int D, const float *obj, const float 
   const int G = dobj ? (O + 15) / 16 : 0;
   const size_t lds = (size_t)(D + O + gps_contra::kWaves) * sizeof(float);
   if (lds > 64 * 1024) return GPS_ERR_UNSUPPORTED;      // (no MaxDynamicSharedMemorySize grant: the default limit; callers fall back)
-  hipLaunchKernelGGL(gps_contra::text_obj_bwd_kernel, dim3(G + 1, B), dim3(gps_contra::kBlock), lds, (hipStream_t)stream, B,
+  hipLaunchKernelGGL(gps_contra::text_obj_bwd_kernel<false>, dim3(G + 1, B), dim3(gps_contra::kBlock), lds, (hipStream_t)stream, B,
                      O, D, G, obj, text, (const int64_t *)labels, eps, ignore_index, cosv, prob, inv_o, inv_t, scal, grad_out,
+                     dobj, dtext);
+  return launch_status();
+}
+
+int gps_text_obj_bce_forward(int B, int O, int D, const float *obj, const float *text, const long long *labels,
+                             const unsigned char *masks, float eps, float *cosv, float *coef, float *inv_o, float *inv_t,
+                             float *loss_rows, float *scal, unsigned int *ticket, gps_stream_t stream) {
+  if (B < 0 || O < 1 || D < 4) return GPS_ERR_INVALID_ARGUMENT;
+  if (B == 0) return GPS_OK;
+  if (!obj || !text || !labels || !masks || !cosv || !coef || !inv_o || !inv_t || !loss_rows || !scal || !ticket)
+    return GPS_ERR_INVALID_ARGUMENT;
+  if ((D & 3) || D > 8192 || O > 4096 || !aligned16(obj) || !aligned16(text)) return GPS_ERR_UNSUPPORTED;
+  const size_t lds = (size_t)(D + O + gps_contra::kFwdWaves) * sizeof(float);
+  if (lds > 64 * 1024) return GPS_ERR_UNSUPPORTED;      // (no MaxDynamicSharedMemorySize grant: the default limit; callers fall back)
+  hipLaunchKernelGGL((gps_contra::text_obj_fwd_kernel<gps_contra::kFwdWaves, true>), dim3(B), dim3(64 * gps_contra::kFwdWaves), lds,
+                     (hipStream_t)stream, B, O, D, obj, text, (const int64_t *)labels, masks, eps, (long long)0, cosv, coef,
+                     inv_o, inv_t, loss_rows, scal, ticket);
+  return launch_status();
+}
+
+int gps_text_obj_bce_backward(int B, int O, int D, const float *obj, const float *text, float eps, const float *cosv,
+                              const float *coef, const float *inv_o, const float *inv_t, const float *scal,
+                              const float *grad_out, float *dobj, float *dtext, gps_stream_t stream) {
+  if (B < 0 || O < 1 || D < 4) return GPS_ERR_INVALID_ARGUMENT;
+  if (B == 0 || (!dobj && !dtext)) return GPS_OK;
+  if (!obj || !text || !cosv || !coef || !inv_o || !inv_t || !scal || !grad_out) return GPS_ERR_INVALID_ARGUMENT;
+  if ((D & 3) || D > 8192 || O > 4096 || !aligned16(obj) || !aligned16(text) || (dobj && !aligned16(dobj)) ||
+      (dtext && !aligned16(dtext)))
+    return GPS_ERR_UNSUPPORTED;
+  const int G = dobj ? (O + 15) / 16 : 0;
+  const size_t lds = (size_t)(D + O + gps_contra::kWaves) * sizeof(float);
+  if (lds > 64 * 1024) return GPS_ERR_UNSUPPORTED;      // (no MaxDynamicSharedMemorySize grant: the default limit; callers fall back)
+  hipLaunchKernelGGL(gps_contra::text_obj_bwd_kernel<true>, dim3(G + 1, B), dim3(gps_contra::kBlock), lds, (hipStream_t)stream, B,
+                     O, D, G, obj, text, (const int64_t *)nullptr, eps, (long long)0, cosv, coef, inv_o, inv_t, scal, grad_out,
                      dobj, dtext);
   return launch_status();
 }

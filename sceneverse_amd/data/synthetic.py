@@ -93,6 +93,33 @@ def synth_batch(batch: int, n_obj: int = 80, n_pts: int = 1024, txt_len: int = 5
     return {k: v.to(device) for k, v in d.items()}
 
 
+def synth_qa_batch(batch: int, n_obj: int = 80, n_pts: int = 1024, txt_len: int = 50, n_answers: int = 8864,
+                   seed: int = 42, n_cls: int = 607, min_real: int | None = None,
+                   device: str | torch.device = "cpu") -> dict:
+    """One `data_dict` of the question-answering fine-tune configurations (reference data/datasets/scanqa.py,
+    sqa3d.py): `synth_batch` (scene captions of length 8: the QA configs do not use them) plus
+      * answer_label (batch, n_answers) int64 multi-hot with 0 - 3 ones per row (0: `use_unanswer: True` keeps the
+        questions whose answers are outside the vocabulary);
+      * tgt_object_id (batch, n_obj) int64 multi-hot over the REAL objects only (1 - 3 ones per scene);
+      * sqa_type (batch,) int64 in 0..5 (what / is / how / can / which / others)."""
+    d = synth_batch(batch, n_obj=n_obj, n_pts=n_pts, txt_len=txt_len, scene_txt_len=8, seed=seed, n_cls=n_cls,
+                    min_real=min_real, device="cpu")
+    rng = np.random.default_rng(seed + 7919)
+    ans = np.zeros((batch, n_answers), dtype=np.int64)
+    tgt = np.zeros((batch, n_obj), dtype=np.int64)
+    masks = d["obj_masks"].numpy()
+    for b in range(batch):
+        k = int(rng.integers(0, min(3, n_answers) + 1))
+        ans[b, rng.choice(n_answers, size=k, replace=False)] = 1
+        real = np.flatnonzero(masks[b])
+        k = int(rng.integers(1, min(3, real.size) + 1))
+        tgt[b, rng.choice(real, size=k, replace=False)] = 1
+    d["answer_label"] = torch.from_numpy(ans)
+    d["tgt_object_id"] = torch.from_numpy(tgt)
+    d["sqa_type"] = torch.from_numpy(rng.integers(0, 6, size=batch).astype(np.int64))
+    return {k: v.to(device) for k, v in d.items()}
+
+
 def adversarial_objects(n_pts: int = 1024, seed: int = 7) -> torch.Tensor:
     """(6, n_pts, 3) xyz clouds that stress the bit-exactness rules of SURVEY.md App. B:
     0 heavy duplicates (FPS ties), 1 many points inside |p|^2 <= 1e-3 (FPS skip rule),

@@ -46,6 +46,7 @@ from __future__ import annotations
 import contextlib
 from typing import Optional
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -753,6 +754,45 @@ def scanrefer_accuracy(og3d_logits: torch.Tensor, iou25_onehot: torch.Tensor,
     hit50 = torch.gather(iou50_onehot, 1, pick).squeeze(1).bool()
     n = float(max(1, pred.shape[0]))
     return {"og_acc_iou25": hit25.sum().item() / n, "og_acc_iou50": hit50.sum().item() / n}
+
+
+def _answer_hits(answer_scores: torch.Tensor, answer_label: torch.Tensor, k: int = 10):
+    """(hit@1, hit@k) per row as bool vectors: the label entry at the arg-max answer / at any of the top-k answers is 1."""
+    top1 = answer_scores.argmax(dim=-1, keepdim=True)
+    topk = torch.topk(answer_scores.detach(), min(k, answer_scores.shape[-1]), -1)[1]
+    hit1 = torch.gather(answer_label, 1, top1).squeeze(1) == 1
+    hitk = (torch.gather(answer_label, 1, topk) == 1).any(dim=1)
+    return hit1, hitk
+
+
+def scanqa_accuracy(answer_scores: torch.Tensor, answer_label: torch.Tensor) -> dict:
+    """ans1_acc / ans10_acc exactly as the reference's ScanQAEval.batch_metrics counts them
+    (evaluator/scanqa_eval.py:29-45 and its division by max(count, 1) at :77-79): a question counts when the multi-hot
+    `answer_label` is set at the arg-max answer / at one of the ten best answers."""
+    hit1, hit10 = _answer_hits(answer_scores, answer_label)
+    n = max(answer_scores.shape[0], 1)
+    return {"ans1_acc": hit1.sum().item() / n, "ans10_acc": hit10.sum().item() / n}
+
+
+def sqa3d_accuracy(answer_scores: torch.Tensor, answer_label: torch.Tensor, sqa_type: torch.Tensor) -> dict:
+    """ans1_acc / ans10_acc plus type{0..5}_acc and type{0..5}_count as the reference's SQA3DEval.batch_metrics returns
+    them (evaluator/sqa3d_eval.py:78-116): the per-type counts start at its 1e-10 floor, so an absent question type gives
+    accuracy 0 and not a division by zero."""
+    hit1, hit10 = _answer_hits(answer_scores, answer_label)
+    n = float(answer_scores.shape[0])
+    types = sqa_type.reshape(-1).to(torch.int64)
+    count = torch.bincount(types, minlength=6)[:6].tolist()
+    correct = torch.bincount(types[hit1], minlength=6)[:6].tolist()
+    out = {"ans1_acc": hit1.sum().item() / n, "ans10_acc": hit10.sum().item() / n}
+    # the reference adds 1 per question to the 1e-10 floor: a sequential running sum gives the same roundings, bit for bit
+    chain = np.cumsum(np.concatenate(([1e-10], np.ones(max(count), dtype=np.float64))))
+    for t in range(6):
+        c = float(chain[count[t]])
+        out[f"type{t}_acc"] = correct[t] / c
+        out[f"type{t}_count"] = c
+    out["target_metric"] = out["ans1_acc"]
+    out["total_count"] = answer_scores.shape[0]
+    return out
 
 
 def dp_self_check(make_engine, batches, rtol_loss: float = 2e-3, rtol_grad: float = 3e-2) -> dict:

@@ -38,7 +38,8 @@ def _symmetric_clip_loss(a, b, logit_scale):
 
 @LOSS_REGISTRY.register()
 class TextObjWithinBatch(nn.Module):
-    """Cross-entropy over the objects of each scene between the sentence CLS and every object."""
+    """Cross-entropy over the objects of each scene between the sentence CLS and every object; with task ScanQA a
+    masked binary cross-entropy against multi-hot targets (B, O)."""
 
     def __init__(self, cfg):
         super().__init__()
@@ -58,6 +59,10 @@ class TextObjWithinBatch(nn.Module):
             from . import fused_contra as FC
             if FC.text_obj_ce_usable(obj_feats, text_feats, labels, masks):
                 return FC.text_obj_ce(obj_feats, text_feats, labels, masks)
+        if self.bce and _FUSED:
+            from . import fused_bce as FB
+            if FB.text_obj_bce_usable(obj_feats, text_feats, labels, masks):
+                return FB.text_obj_bce(obj_feats, text_feats, labels, masks)
         obj_feats = l2_normalize(obj_feats)
         text_feats = l2_normalize(text_feats)
         logits = torch.einsum('bod,bd->bo', obj_feats, text_feats)

@@ -3,7 +3,7 @@
 
 Reference: optim/loss/contra_loss.py:22-43 (TextObjWithinBatch, cross-entropy branch) and :11-17 + :57-60 / :79-83
 (_symmetric_clip_loss over F.normalize'd rows with the clamped logit scale).  fp32 GPU tensors; anything else keeps
-the torch composition in contra_loss.py (CPU tensors, the BCE branch)."""
+the torch composition in contra_loss.py (CPU tensors); the BCE branch of TextObjWithinBatch is fused_bce.text_obj_bce."""
 from __future__ import annotations
 
 import torch

@@ -57,7 +57,16 @@ def obj_cls_post_loss(data_dict):                           # ref :42-47
     return _masked_obj_ce("obj_cls_post_logits", data_dict, _w_all)
 
 
+_FUSED_BCE = True    # tests / A-B runs: False = the torch composition on GPU tensors too
+
+
 def answer_loss(data_dict):                                 # ref :50-53
+    scores, labels = data_dict["answer_scores"], data_dict["answer_label"]
+    if _FUSED_BCE and scores.is_cuda:
+        # one launch per direction, the int64 multi-hot labels read in place (csrc/gps_qa.hip)
+        from .fused_bce import bce_logits_sum, bce_logits_usable
+        if bce_logits_usable(scores, labels):
+            return bce_logits_sum(scores, labels, None, 1.0 / scores.shape[0])
     return F.binary_cross_entropy_with_logits(
         data_dict["answer_scores"], data_dict["answer_label"].float(),
         reduction='sum') / data_dict["answer_scores"].shape[0]
