@@ -581,6 +581,44 @@ GPS_API int gps_obj_processing_post(int n_rows, int n_points, const float *xyz, 
                                     const int32_t *row_rot, float *obj_fts, float *obj_locs, float *obj_boxes,
                                     uint8_t *obj_masks, gps_stream_t stream);
 
+/* ---- the same, through the augmented path ------------------------------------------------------------
+ * Replaces ScanBase._obj_processing_aug (data/datasets/base.py:742-776) together with
+ * DataAugmentor.update_data_dict (data/datasets/data_augmentor.py:156-215): the branch every config with a
+ * `data_aug:` block takes, on the training AND the validation split.  Per object: flip (x @ F), scale about the
+ * mean of ALL its points, subsample n_points, jitter x += (z - 0.5) * scale, size = max - min of the sample,
+ * scene + object translation, scene rotation (x @ R, not R.T), object rotation about the sample mean, colour
+ * delta; then centre = sample mean, box centre = (min + max) / 2, obj_locs = [centre, size], obj_boxes =
+ * [box centre, size], x -= centre, x /= max(max ||x||, 1e-6).  The point shuffle needs no argument: pass
+ * sample_idx / jitter_noise already permuted (device-drawn samples are in random order anyway).
+ *   xyz, rgb, rgb_is_u8, obj_offsets, row_obj, sample_idx, seed and the four outputs: as gps_obj_processing_post.
+ *   aug (n_aug, GPS_OBJ_AUG_STRIDE) float64 + row_aug (n_rows) int32 (entry of output row r; < 0 or >= n_aug =
+ *   nothing applied), both NULL = no augmentation at all (the validation split).  One entry, in doubles:
+ *     [0] presence flags, the sum of the GPS_OBJ_AUG_* bits of what the entry applies
+ *     [1] scale   [2..4] jitter scale x, y, z   [5..7] scene translation   [8..10] object translation
+ *     [11..13] rgb delta   [14..22] flip 3x3   [23..31] scene rotation 3x3   [32..40] object rotation 3x3
+ *     (matrices row-major, applied as x @ M)   [41..47] reserved, 0.
+ *   float64 because rounding a translation of ~1 to f32 already costs half an ulp of the result.
+ *   jitter_noise (n_rows, n_points, 3) standard-normal draws, f32 or (noise_is_f64 != 0) f64, for replays of the
+ *   reference's np.random.randn; NULL = drawn on the device (Box-Muller on the mix64 stream keyed by seed, row,
+ *   point and coordinate, independent of the sampler's key).  Read only by rows whose entry has the jitter bit.
+ * Only rows with the scale bit read all points of their object; n_points <= 2048.  Arithmetic in float64, the
+ * sizes rounded from their float64 value, everything else rounded to f32 at the end. */
+#define GPS_OBJ_AUG_STRIDE 48
+#define GPS_OBJ_AUG_FLIP 1
+#define GPS_OBJ_AUG_SCALE 2
+#define GPS_OBJ_AUG_SCENE_TRANS 4
+#define GPS_OBJ_AUG_SCENE_ROT 8
+#define GPS_OBJ_AUG_RGB 16
+#define GPS_OBJ_AUG_OBJ_TRANS 32
+#define GPS_OBJ_AUG_OBJ_ROT 64
+#define GPS_OBJ_AUG_JITTER 128
+GPS_API int gps_obj_processing_aug(int n_rows, int n_points, const float *xyz, const void *rgb, int rgb_is_u8,
+                                   const int64_t *obj_offsets, const int32_t *row_obj,
+                                   const int32_t *sample_idx, const void *jitter_noise, int noise_is_f64,
+                                   uint64_t seed, const double *aug, const int32_t *row_aug, int n_aug,
+                                   float *obj_fts, float *obj_locs, float *obj_boxes, uint8_t *obj_masks,
+                                   gps_stream_t stream);
+
 /* ---- bias gradients: column sums of a bf16 matrix ---------------------------------------------------
  * Replaces the `dY.sum(0)` autograd derives for the bias of every nn.Linear in the transformer stacks
  * (modules/layers/transformers.py:115-154, 285-316; HF BertLayer behind modules/language/bert.py:21-26).

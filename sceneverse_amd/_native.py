@@ -111,6 +111,8 @@ SIGNATURES = {
     "gps_sa_mlp_forward_bf16x3_pm": [_i] * 8 + [_vp] * 3 + [ctypes.c_longlong] + [_vp] * 4,
     "gps_obj_processing_post": [_i, _i, _vp, _vp, _i, _vp, _vp, _vp, ctypes.c_ulonglong, _vp, _vp, _vp, _vp, _vp,
                                 _vp, _vp],
+    "gps_obj_processing_aug": [_i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, ctypes.c_ulonglong, _vp, _vp, _i,
+                               _vp, _vp, _vp, _vp, _vp],
     "gps_embedding_grad_scratch_ints": [_i, _i, _i],
     "gps_embedding_grad": [_i, _i, _i, _vp, _vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, _vp],
     "gps_loc_embed_partial_rows": [_i],

@@ -284,3 +284,278 @@ extern "C" int gps_obj_processing_post(int n_rows, int n_points, const float *xy
   }
   return hipGetLastError() == hipSuccess ? GPS_OK : GPS_ERR_LAUNCH;
 }
+
+// ---- the augmented path ------------------------------------------------------------------------------
+// Reference: ScanBase._obj_processing_aug, data/datasets/base.py:742-776, fed by DataAugmentor.update_data_dict,
+// data/datasets/data_augmentor.py:156-215 -- the branch every config with a `data_aug:` block takes (train AND val).
+// It is a different function from _post: it subsamples FIRST, takes the object size from the (jittered) sample before
+// any translation / rotation, centre and box from the transformed sample, rotates as x @ R (not x @ R.T) and clamps
+// max_dist at 1e-6.  Order per object: flip, scale about the mean of ALL points, subsample, jitter, size, scene +
+// object translation, scene rotation, object rotation about the sample mean, colour delta, centre, unit ball.
+//
+// One workgroup per output row, the sampled points in VGPRs as above.  Only a row whose scale is on walks all k points
+// of its object, and then only to sum them (flip is linear: the mean of the flipped points is the flipped mean);
+// every other row touches the num_points gathered records alone.  The point shuffle (data_augmentor.py:211-212) needs
+// no work here: every later step is a per-point map or an order-free reduction, so a permutation of the sample rows
+// is a permutation of the (sample_idx, jitter_noise) the caller passes; device-drawn samples are already in random order.
+// Arithmetic in float64 with block reductions, the sizes rounded from their float64 value, everything else rounded to
+// f32 at the end (the reference rounds to f32 earlier -- at the scene rotation or at the tensor conversion; the
+// difference is its rounding noise, tests/test_gpu_objects_aug.py).
+namespace gps_obj {
+
+// Components [0, NS) are summed, [NS, NS + NMIN) minimised, the rest maximised; every thread gets the results.
+template <int NS, int NMIN, int NMAX>
+__device__ __forceinline__ void block_reduce(double *v, double (*s_red)[9], double *s_out, int tid) {
+  constexpr int N = NS + NMIN + NMAX;
+  static_assert(N <= 9, "s_red / s_out hold nine components");
+  const int lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+  for (int c = 0; c < N; ++c) v[c] = c < NS ? wave_sum(v[c]) : (c < NS + NMIN ? wave_min(v[c]) : wave_max(v[c]));
+  if (lane == 0) {
+#pragma unroll
+    for (int c = 0; c < N; ++c) s_red[wave][c] = v[c];
+  }
+  __syncthreads();
+  if (tid < N) {
+    double r = s_red[0][tid];
+    for (int w = 1; w < kWaves; ++w)
+      r = tid < NS ? r + s_red[w][tid] : (tid < NS + NMIN ? fmin(r, s_red[w][tid]) : fmax(r, s_red[w][tid]));
+    s_out[tid] = r;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int c = 0; c < N; ++c) v[c] = s_out[c];
+}
+
+// x @ M for a row-major 3x3 (np.matmul(x, mat), data_augmentor.py:245-251): out_j = sum_c p_c * M[c][j]
+__device__ __forceinline__ void mul_right(const double *__restrict__ m, double &x, double &y, double &z) {
+  const double a = (x * m[0] + y * m[3]) + z * m[6];
+  const double b = (x * m[1] + y * m[4]) + z * m[7];
+  const double c = (x * m[2] + y * m[5]) + z * m[8];
+  x = a; y = b; z = c;
+}
+
+// Standard normal for (row key, point, coordinate): Box-Muller on two words of the mix64 stream.
+__device__ __forceinline__ double normal_draw(uint64_t key, uint32_t j, uint32_t c) {
+  const uint64_t h1 = mix64(key ^ (((uint64_t)j << 2 | c) << 1));
+  const uint64_t h2 = mix64(h1 ^ 0xC2B2AE3D27D4EB4Full);
+  const double u1 = (double)((h1 >> 11) + 1ull) * 0x1.0p-53;          // (0, 1]
+  const double u2 = (double)(h2 >> 11) * 0x1.0p-53;                   // [0, 1)
+  return sqrt(-2.0 * log(u1)) * cospi(2.0 * u2);
+}
+
+// layout of one entry of the parameter table (doubles), include/gps_hip.h
+constexpr int kAugStride = GPS_OBJ_AUG_STRIDE;
+constexpr int kAugScale = 1, kAugJitter = 2, kAugSceneTrans = 5, kAugObjTrans = 8, kAugRgb = 11, kAugFlip = 14,
+              kAugSceneRot = 23, kAugObjRot = 32;
+
+template <bool REC16>
+__global__ __launch_bounds__(kBlock) void obj_processing_aug_kernel(
+    int n_points, const float *__restrict__ xyz, const uint8_t *__restrict__ rgb_u8,
+    const float *__restrict__ rgb_f32, const int64_t *__restrict__ obj_offsets,
+    const int32_t *__restrict__ row_obj, const int32_t *__restrict__ sample_idx,
+    const float *__restrict__ noise_f32, const double *__restrict__ noise_f64, uint64_t seed,
+    const double *__restrict__ aug, const int32_t *__restrict__ row_aug, int n_aug, float *__restrict__ obj_fts,
+    float *__restrict__ obj_locs, float *__restrict__ obj_boxes, uint8_t *__restrict__ obj_masks) {
+  __shared__ double s_red[kWaves][9];
+  __shared__ double s_out[9];
+  const int row = blockIdx.x, tid = threadIdx.x;
+  const int obj = row_obj[row];
+  float *fts = obj_fts + (size_t)row * n_points * 6;
+  int64_t begin = 0, k64 = 0;
+  if (obj >= 0) {
+    begin = obj_offsets[obj];
+    k64 = obj_offsets[obj + 1] - begin;
+  }
+  if (obj < 0 || k64 <= 0) {                    // padding slot: features 1.0, locations 0.0, mask off
+    for (int i = tid; i < n_points * 6; i += kBlock) fts[i] = 1.0f;
+    if (tid < 6) {
+      obj_locs[(size_t)row * 6 + tid] = 0.0f;
+      if (obj_boxes) obj_boxes[(size_t)row * 6 + tid] = 0.0f;
+    }
+    if (tid == 0 && obj_masks) obj_masks[row] = 0;
+    return;
+  }
+  const uint32_t k = (uint32_t)k64;
+  const int set = aug != nullptr ? row_aug[row] : -1;
+  const double *A = aug + (size_t)(set >= 0 && set < n_aug ? set : 0) * kAugStride;
+  const uint32_t flags = set >= 0 && set < n_aug ? (uint32_t)A[0] : 0u;
+  const float *p = xyz + (size_t)begin * (REC16 ? 4 : 3);
+  const float4 *p4 = reinterpret_cast<const float4 *>(xyz) + begin;
+
+  // ---- scale only: the mean of ALL points (a sum; flip is applied to the mean) ----------------
+  double cs[3] = {0, 0, 0};
+  if (flags & GPS_OBJ_AUG_SCALE) {
+    uint32_t i = tid;
+    if (REC16) {
+      for (; i + 3u * kBlock < k; i += 4u * kBlock) {
+        const float4 r0 = p4[i], r1 = p4[i + kBlock], r2 = p4[i + 2u * kBlock], r3 = p4[i + 3u * kBlock];
+        cs[0] += ((double)r0.x + (double)r1.x) + ((double)r2.x + (double)r3.x);
+        cs[1] += ((double)r0.y + (double)r1.y) + ((double)r2.y + (double)r3.y);
+        cs[2] += ((double)r0.z + (double)r1.z) + ((double)r2.z + (double)r3.z);
+      }
+      for (; i < k; i += kBlock) {
+        const float4 r = p4[i];
+        cs[0] += r.x; cs[1] += r.y; cs[2] += r.z;
+      }
+    } else {
+      for (; i < k; i += kBlock) {
+        cs[0] += p[(size_t)i * 3]; cs[1] += p[(size_t)i * 3 + 1]; cs[2] += p[(size_t)i * 3 + 2];
+      }
+    }
+    block_reduce<3, 0, 0>(cs, s_red, s_out, tid);
+    cs[0] /= (double)k; cs[1] /= (double)k; cs[2] /= (double)k;
+    if (flags & GPS_OBJ_AUG_FLIP) mul_right(A + kAugFlip, cs[0], cs[1], cs[2]);
+  }
+
+  // ---- the sampled points, held in registers: flip, scale, jitter -> size ---------------------
+  const bool replace = k < (uint32_t)n_points;
+  const uint64_t key = mix64(seed ^ mix64((uint64_t)row));   // per output row: a scene drawn twice differs
+  const uint64_t nkey = mix64(key ^ 0x6A09E667F3BCC909ull);  // the jitter stream, independent of the sampler's
+  double px[kMaxPer], py[kMaxPer], pz[kMaxPer];
+  uint32_t src[kMaxPer];                         // sampled index, or (REC16) the record's colour word
+  double mm[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
+#pragma unroll
+  for (int i = 0; i < kMaxPer; ++i) {
+    const int j = tid + i * kBlock;
+    if (j < n_points) {
+      uint32_t s = sample_idx ? (uint32_t)sample_idx[(size_t)row * n_points + j]
+                              : sample_index(key, (uint32_t)j, k, replace);
+      s = s < k ? s : k - 1;                     // a caller-supplied index is clamped, never trusted
+      double x, y, z;
+      if (REC16) {
+        const float4 r = p4[s];
+        x = r.x; y = r.y; z = r.z;
+        src[i] = __float_as_uint(r.w);
+      } else {
+        x = p[(size_t)s * 3]; y = p[(size_t)s * 3 + 1]; z = p[(size_t)s * 3 + 2];
+        src[i] = s;
+      }
+      if (flags & GPS_OBJ_AUG_FLIP) mul_right(A + kAugFlip, x, y, z);
+      if (flags & GPS_OBJ_AUG_SCALE) {           // (x - c) * s + c, data_augmentor.py:254-256
+        const double sc = A[kAugScale];
+        x = (x - cs[0]) * sc + cs[0]; y = (y - cs[1]) * sc + cs[1]; z = (z - cs[2]) * sc + cs[2];
+      }
+      if (flags & GPS_OBJ_AUG_JITTER) {          // x + (randn - 0.5) * scale, data_augmentor.py:259-260
+        double nx, ny, nz;
+        const size_t q = ((size_t)row * n_points + j) * 3;
+        if (noise_f64) {
+          nx = noise_f64[q]; ny = noise_f64[q + 1]; nz = noise_f64[q + 2];
+        } else if (noise_f32) {
+          nx = noise_f32[q]; ny = noise_f32[q + 1]; nz = noise_f32[q + 2];
+        } else {
+          nx = normal_draw(nkey, (uint32_t)j, 0); ny = normal_draw(nkey, (uint32_t)j, 1);
+          nz = normal_draw(nkey, (uint32_t)j, 2);
+        }
+        x += (nx - 0.5) * A[kAugJitter]; y += (ny - 0.5) * A[kAugJitter + 1]; z += (nz - 0.5) * A[kAugJitter + 2];
+      }
+      px[i] = x; py[i] = y; pz[i] = z;
+      mm[0] = fmin(mm[0], x); mm[1] = fmin(mm[1], y); mm[2] = fmin(mm[2], z);
+      mm[3] = fmax(mm[3], x); mm[4] = fmax(mm[4], y); mm[5] = fmax(mm[5], z);
+    }
+  }
+  block_reduce<0, 3, 3>(mm, s_red, s_out, tid);
+  const double size[3] = {mm[3] - mm[0], mm[4] - mm[1], mm[5] - mm[2]};   // before translation and rotation
+
+  // ---- translate, scene rotation -> sample mean ------------------------------------------------
+  double ctr[3] = {0, 0, 0};
+#pragma unroll
+  for (int i = 0; i < kMaxPer; ++i) {
+    const int j = tid + i * kBlock;
+    if (j < n_points) {
+      if (flags & GPS_OBJ_AUG_SCENE_TRANS) {
+        px[i] += A[kAugSceneTrans]; py[i] += A[kAugSceneTrans + 1]; pz[i] += A[kAugSceneTrans + 2];
+      }
+      if (flags & GPS_OBJ_AUG_OBJ_TRANS) {
+        px[i] += A[kAugObjTrans]; py[i] += A[kAugObjTrans + 1]; pz[i] += A[kAugObjTrans + 2];
+      }
+      if (flags & GPS_OBJ_AUG_SCENE_ROT) mul_right(A + kAugSceneRot, px[i], py[i], pz[i]);
+      ctr[0] += px[i]; ctr[1] += py[i]; ctr[2] += pz[i];
+    }
+  }
+  block_reduce<3, 0, 0>(ctr, s_red, s_out, tid);
+  ctr[0] /= (double)n_points; ctr[1] /= (double)n_points; ctr[2] /= (double)n_points;
+
+  // ---- centre (the object rotation turns about it and so leaves it in place), box, farthest point ---
+  double bx[7] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY, 0.0};
+#pragma unroll
+  for (int i = 0; i < kMaxPer; ++i) {
+    const int j = tid + i * kBlock;
+    if (j < n_points) {
+      px[i] -= ctr[0]; py[i] -= ctr[1]; pz[i] -= ctr[2];
+      if (flags & GPS_OBJ_AUG_OBJ_ROT) mul_right(A + kAugObjRot, px[i], py[i], pz[i]);
+      bx[0] = fmin(bx[0], px[i]); bx[1] = fmin(bx[1], py[i]); bx[2] = fmin(bx[2], pz[i]);
+      bx[3] = fmax(bx[3], px[i]); bx[4] = fmax(bx[4], py[i]); bx[5] = fmax(bx[5], pz[i]);
+      bx[6] = fmax(bx[6], sqrt((px[i] * px[i] + py[i] * py[i]) + pz[i] * pz[i]));
+    }
+  }
+  block_reduce<0, 3, 4>(bx, s_red, s_out, tid);
+  if (tid < 3) {
+    obj_locs[(size_t)row * 6 + tid] = (float)ctr[tid];
+    obj_locs[(size_t)row * 6 + 3 + tid] = (float)size[tid];
+    if (obj_boxes) {
+      obj_boxes[(size_t)row * 6 + tid] = (float)((bx[tid] + bx[3 + tid]) / 2.0 + ctr[tid]);
+      obj_boxes[(size_t)row * 6 + 3 + tid] = (float)size[tid];
+    }
+  }
+  if (tid == 0 && obj_masks) obj_masks[row] = 1;
+  const double max_dist = fmax(bx[6], 1e-6);     // clamp_(min=1e-6), base.py:768 -- not "-> 1" as in _post
+  double dr = 0, dg = 0, db = 0;
+  if (flags & GPS_OBJ_AUG_RGB) { dr = A[kAugRgb]; dg = A[kAugRgb + 1]; db = A[kAugRgb + 2]; }
+#pragma unroll
+  for (int i = 0; i < kMaxPer; ++i) {
+    const int j = tid + i * kBlock;
+    if (j < n_points) {
+      float *o = fts + (size_t)j * 6;
+      o[0] = (float)(px[i] / max_dist);
+      o[1] = (float)(py[i] / max_dist);
+      o[2] = (float)(pz[i] / max_dist);
+      const size_t c = ((size_t)begin + src[i]) * 3;
+      double r, g, b;
+      if (REC16) {                               // colours came with the record (little-endian r, g, b)
+        r = (double)(src[i] & 255u) / 127.5 - 1.0;
+        g = (double)((src[i] >> 8) & 255u) / 127.5 - 1.0;
+        b = (double)((src[i] >> 16) & 255u) / 127.5 - 1.0;
+      } else if (rgb_u8) {                       // colors / 127.5 - 1 in f64 (uint8 promotes)
+        r = (double)rgb_u8[c] / 127.5 - 1.0;
+        g = (double)rgb_u8[c + 1] / 127.5 - 1.0;
+        b = (double)rgb_u8[c + 2] / 127.5 - 1.0;
+      } else {                                   // float32 colours are scaled in float32 by the loader (numpy's rules)
+        r = rgb_f32[c] / 127.5f - 1.0f;
+        g = rgb_f32[c + 1] / 127.5f - 1.0f;
+        b = rgb_f32[c + 2] / 127.5f - 1.0f;
+      }
+      o[3] = (float)(r + dr); o[4] = (float)(g + dg); o[5] = (float)(b + db);
+    }
+  }
+}
+
+}  // namespace gps_obj
+
+extern "C" int gps_obj_processing_aug(int n_rows, int n_points, const float *xyz, const void *rgb, int rgb_is_u8,
+                                      const int64_t *obj_offsets, const int32_t *row_obj,
+                                      const int32_t *sample_idx, const void *jitter_noise, int noise_is_f64,
+                                      uint64_t seed, const double *aug, const int32_t *row_aug, int n_aug,
+                                      float *obj_fts, float *obj_locs, float *obj_boxes, uint8_t *obj_masks,
+                                      gps_stream_t stream) {
+  if (n_rows < 0 || n_points <= 0) return GPS_ERR_INVALID_ARGUMENT;
+  if (n_points > gps_obj::kBlock * gps_obj::kMaxPer) return GPS_ERR_UNSUPPORTED;
+  if (n_rows == 0) return GPS_OK;
+  if (!xyz || !obj_offsets || !row_obj || !obj_fts || !obj_locs) return GPS_ERR_INVALID_ARGUMENT;
+  if ((aug == nullptr) != (row_aug == nullptr)) return GPS_ERR_INVALID_ARGUMENT;
+  if (aug && n_aug <= 0) return GPS_ERR_INVALID_ARGUMENT;
+  const float *n32 = noise_is_f64 ? nullptr : (const float *)jitter_noise;
+  const double *n64 = noise_is_f64 ? (const double *)jitter_noise : nullptr;
+  if (!rgb) {                                    // 16-byte records: colours travel in the 4th word
+    if (((uintptr_t)xyz & 15u) != 0) return GPS_ERR_INVALID_ARGUMENT;
+    hipLaunchKernelGGL(gps_obj::obj_processing_aug_kernel<true>, dim3(n_rows), dim3(gps_obj::kBlock), 0,
+                       (hipStream_t)stream, n_points, xyz, nullptr, nullptr, obj_offsets, row_obj, sample_idx, n32, n64,
+                       seed, aug, row_aug, n_aug, obj_fts, obj_locs, obj_boxes, obj_masks);
+  } else {
+    hipLaunchKernelGGL(gps_obj::obj_processing_aug_kernel<false>, dim3(n_rows), dim3(gps_obj::kBlock), 0,
+                       (hipStream_t)stream, n_points, xyz, rgb_is_u8 ? (const uint8_t *)rgb : nullptr,
+                       rgb_is_u8 ? nullptr : (const float *)rgb, obj_offsets, row_obj, sample_idx, n32, n64, seed, aug,
+                       row_aug, n_aug, obj_fts, obj_locs, obj_boxes, obj_masks);
+  }
+  return hipGetLastError() == hipSuccess ? GPS_OK : GPS_ERR_LAUNCH;
+}

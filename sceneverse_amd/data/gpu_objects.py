@@ -4,6 +4,8 @@ Reference (what this replaces on the data-loader workers):
     ScanBase._load_scan            data/datasets/base.py:65-142   per scan: pcds = [points | colors/127.5-1],
                                                                   obj_pcds = [pcds[instance_labels == id] ...]
     ScanBase._obj_processing_post  data/datasets/base.py:697-740  rotate, obj_locs, box, subsample, normalise
+    ScanBase._obj_processing_aug   data/datasets/base.py:742-776  the branch of every config with a `data_aug:` block
+    DataAugmentor                  data/datasets/data_augmentor.py  its draws (:39-154) and their application (:156-215)
     dataset wrapper padding        data/datasets/dataset_wrapper.py:62-70  pad to max_obj_len, obj_masks
 
 MI355X form: every scan is uploaded ONCE in its raw on-disk precision (xyz f32 + rgb u8, packed as
@@ -16,7 +18,9 @@ the CPU path; oracle/obj_processing.py restates it for the tests).
 """
 from __future__ import annotations
 
-from typing import Dict, List, Optional, Sequence
+import math
+from dataclasses import dataclass
+from typing import Dict, List, Mapping, Optional, Sequence
 
 import numpy as np
 import torch
@@ -171,6 +175,258 @@ def obj_processing_post(packed: PackedScans, row_obj: torch.Tensor, num_points: 
     return res
 
 
+# ---- the augmented path: ScanBase._obj_processing_aug + DataAugmentor ---------------------------------
+AUG_STRIDE = 48                                  # GPS_OBJ_AUG_STRIDE of include/gps_hip.h, and the offsets of its comment
+AUG_FLIP, AUG_SCALE, AUG_SCENE_TRANS, AUG_SCENE_ROT, AUG_RGB, AUG_OBJ_TRANS, AUG_OBJ_ROT, AUG_JITTER = (
+    1, 2, 4, 8, 16, 32, 64, 128)
+# (AugParams field, presence bit, first double of the entry, doubles) of the per-scene knobs
+_AUG_SCENE = (("scene_flip", AUG_FLIP, 14, 9), ("scene_scale", AUG_SCALE, 1, 1), ("scene_trans", AUG_SCENE_TRANS, 5, 3),
+              ("scene_rot", AUG_SCENE_ROT, 23, 9), ("rgb_delta", AUG_RGB, 11, 3), ("obj_jitter", AUG_JITTER, 2, 3))
+_AUG_OBJ_TRANS_AT, _AUG_OBJ_ROT_AT = 8, 32
+
+
+@dataclass
+class AugParams:
+    """One batch's draws of DataAugmentor (the `aug_dict` of data_augmentor.py:218-223, per scene).  Every field is
+    a length-B list (or None = absent for the whole batch); an entry None means "not applied" to that scene.
+
+    scene_flip / scene_rot: (3,3) float64, applied as x @ M.  scene_scale: float.  scene_trans / rgb_delta: (3,).
+    obj_trans / obj_rot: per scene a length-O list over the object SLOTS of `row_obj` (None = that object keeps
+    its place) of (3,) / (3,3).  obj_jitter: the jitter scale, a float or (3,).  pts_shuffle: bool per scene -- kept
+    for the record only: a permutation of the sample rows commutes with everything downstream, so it is realised by
+    the order of the draws (device-drawn samples are in random order; a replay passes permuted sample_idx and
+    jitter_noise), never by device work."""
+    scene_flip: Optional[list] = None
+    scene_scale: Optional[list] = None
+    scene_trans: Optional[list] = None
+    scene_rot: Optional[list] = None
+    rgb_delta: Optional[list] = None
+    obj_trans: Optional[list] = None
+    obj_rot: Optional[list] = None
+    obj_jitter: Optional[list] = None
+    pts_shuffle: Optional[list] = None
+
+    def _get(self, name: str, b: int):
+        v = getattr(self, name)
+        return None if v is None else v[b]
+
+    def table(self, B: int, O: int):
+        """-> (entries (n, AUG_STRIDE) float64, row_aug (B*O,) int32 with -1 = nothing applied).  A scene without
+        per-object parameters is ONE entry shared by its O rows (the published configs: B entries per batch)."""
+        entries, row_aug = [], np.full((B, O), -1, dtype=np.int32)
+        for b in range(B):
+            e, flags = np.zeros(AUG_STRIDE, dtype=np.float64), 0
+            for name, bit, at, n in _AUG_SCENE:
+                v = self._get(name, b)
+                if v is not None:                 # a scalar jitter scale serves all three coordinates
+                    e[at:at + n] = np.broadcast_to(np.asarray(v, dtype=np.float64).reshape(-1), (n,))
+                    flags |= bit
+            ot, orot = self._get("obj_trans", b), self._get("obj_rot", b)
+            per_obj = any(x is not None for x in (ot or [])) or any(x is not None for x in (orot or []))
+            if not per_obj:
+                if flags:
+                    e[0] = flags
+                    row_aug[b, :] = len(entries)
+                    entries.append(e)
+                continue
+            for o in range(O):
+                eo, fo = e.copy(), flags
+                if ot is not None and o < len(ot) and ot[o] is not None:
+                    eo[_AUG_OBJ_TRANS_AT:_AUG_OBJ_TRANS_AT + 3] = np.asarray(ot[o], dtype=np.float64).reshape(3)
+                    fo |= AUG_OBJ_TRANS
+                if orot is not None and o < len(orot) and orot[o] is not None:
+                    eo[_AUG_OBJ_ROT_AT:_AUG_OBJ_ROT_AT + 9] = np.asarray(orot[o], dtype=np.float64).reshape(9)
+                    fo |= AUG_OBJ_ROT
+                if fo:
+                    eo[0] = fo
+                    row_aug[b, o] = len(entries)
+                    entries.append(eo)
+        tab = np.stack(entries, 0) if entries else np.zeros((0, AUG_STRIDE), dtype=np.float64)
+        return tab, row_aug.reshape(-1)
+
+    def to_device(self, B: int, O: int, dev) -> "AugTable":
+        tab, row_aug = self.table(B, O)
+        return AugTable(torch.from_numpy(tab).to(dev), torch.from_numpy(row_aug).to(dev),
+                        bool((tab[:, 0].astype(np.int64) & AUG_SCALE).any()))
+
+
+@dataclass
+class AugTable:
+    """AugParams.table() on the device: what the launch reads.  Build it ahead of the step (AugParams.to_device) to
+    keep the upload out of a captured or timed region."""
+    entries: torch.Tensor                        # (n, AUG_STRIDE) float64
+    row_aug: torch.Tensor                        # (B*O,) int32, -1 = nothing applied
+    has_scale: bool                              # some entry scales: those rows read all points of their object
+
+
+def obj_processing_aug(packed: PackedScans, row_obj: torch.Tensor, num_points: int = 1024,
+                       aug: "Optional[AugParams | AugTable]" = None, sample_idx: Optional[torch.Tensor] = None,
+                       jitter_noise: Optional[torch.Tensor] = None, seed: int = 0, need_boxes: bool = False,
+                       out: Optional[dict] = None) -> dict:
+    """ScanBase._obj_processing_aug (base.py:742-776) after DataAugmentor.update_data_dict (data_augmentor.py:156-215)
+    for a whole batch in one launch; same return dict and the same in-place `out=` contract as obj_processing_post
+    (so it fills `GPSTrainStep.static_inputs()` just the same).
+
+    aug: the batch's AugParams (`draw_aug_params`) or their AugTable already on the device, or None = nothing applied -- the reference's validation path under
+    a `data_aug` config (an empty augmentor queue still takes this branch: subsample, sizes / centres from the sample,
+    max_dist clamped at 1e-6).
+    sample_idx (B,O,num_points) int32 / jitter_noise (B,O,num_points,3) float32 or float64: the reference's
+    np.random.choice / np.random.randn draws for a replay -- already in the order the point shuffle left them; None =
+    drawn on the device from `seed` (the noise only for scenes whose obj_jitter is set)."""
+    if packed.xyz is None:
+        raise RuntimeError("PackedScans.finalize() has not been called")
+    dev = packed.xyz.device
+    if dev.type != "cuda":
+        raise RuntimeError("obj_processing_aug runs on libgps_hip.so: scenes must live on a GPU (no CPU path)")
+    B, O = row_obj.shape
+    n_rows = B * O
+    if isinstance(aug, AugParams):
+        aug = aug.to_device(B, O, dev)
+    tab, row_aug, scaled = (aug.entries, aug.row_aug, aug.has_scale) if aug is not None else (None, None, False)
+    if tab is not None and (tab.shape[0] == 0 or row_aug.shape[0] != n_rows):
+        if tab.shape[0]:
+            raise ValueError(f"obj_processing_aug: the parameter table indexes {row_aug.shape[0]} rows, the batch has {n_rows}")
+        tab = row_aug = None
+    nbytes = _algorithmic_bytes(packed, row_obj if row_obj.device.type == "cpu" else None, n_rows, num_points,
+                                stream_all=scaled)
+    row_obj = row_obj.to(device=dev, dtype=torch.int32).contiguous()
+    if out is not None:
+        fts, locs, masks = out["obj_fts"], out["obj_locs"], out["obj_masks"]
+        ok = (fts.shape == (B, O, num_points, 6) and fts.dtype == torch.float32 and locs.shape == (B, O, 6)
+              and locs.dtype == torch.float32 and masks.shape == (B, O) and masks.dtype in (torch.bool, torch.uint8)
+              and all(t.is_contiguous() and t.device == dev for t in (fts, locs, masks)))
+        if not ok:
+            raise ValueError("obj_processing_aug: `out` tensors must be contiguous (B,O,P,6) f32 / (B,O,6) f32 / (B,O) bool on the scans' GPU")
+    else:
+        fts = torch.empty((B, O, num_points, 6), dtype=torch.float32, device=dev)
+        locs = torch.empty((B, O, 6), dtype=torch.float32, device=dev)
+        masks = torch.empty((B, O), dtype=torch.uint8, device=dev)
+    boxes = torch.empty((B, O, 6), dtype=torch.float32, device=dev) if need_boxes else None
+    if sample_idx is not None:
+        sample_idx = sample_idx.to(device=dev, dtype=torch.int32).contiguous()
+        assert sample_idx.shape == (B, O, num_points), sample_idx.shape
+    if jitter_noise is not None:
+        if jitter_noise.dtype not in (torch.float32, torch.float64):
+            raise ValueError("obj_processing_aug: jitter_noise must be float32 or float64")
+        jitter_noise = jitter_noise.to(device=dev).contiguous()
+        assert jitter_noise.shape == (B, O, num_points, 3), jitter_noise.shape
+    from ..pointnet2._ext import _timed
+    with torch.cuda.device(dev), _timed(f"obj_processing_aug(rows={n_rows},P={num_points})", nbytes):
+        st = _native.load().gps_obj_processing_aug(
+            n_rows, num_points, packed.xyz.data_ptr(), packed.rgb.data_ptr() if packed.rgb is not None else None,
+            int(packed.rgb is None or packed.rgb.dtype == torch.uint8),
+            packed.obj_offsets.data_ptr(), row_obj.data_ptr(),
+            sample_idx.data_ptr() if sample_idx is not None else None,
+            jitter_noise.data_ptr() if jitter_noise is not None else None,
+            int(jitter_noise is not None and jitter_noise.dtype == torch.float64), int(seed) & ((1 << 64) - 1),
+            tab.data_ptr() if tab is not None else None, row_aug.data_ptr() if tab is not None else None,
+            tab.shape[0] if tab is not None else 0,
+            fts.data_ptr(), locs.data_ptr(), boxes.data_ptr() if need_boxes else None,
+            masks.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    _native.check(st, "obj_processing_aug")
+    res = {"obj_fts": fts, "obj_locs": locs, "obj_masks": masks if masks.dtype == torch.bool else masks.bool()}
+    if need_boxes:
+        res["obj_boxes"] = boxes
+    return res
+
+
+def _check_key(key) -> bool:
+    """DataAugmentor.check_key (data_augmentor.py:225-238): absent -> off, a bool is itself, a mapping is its
+    `enabled` (default on), anything else is on."""
+    if key is None:
+        return False
+    if isinstance(key, bool):
+        return key
+    if isinstance(key, Mapping):
+        return bool(key.get("enabled", True))
+    return True
+
+
+def _check_p(key, rng: np.random.Generator) -> bool:
+    """DataAugmentor.check_p (data_augmentor.py:241-242): a mapping with a `p` fires with that probability, and the
+    draw is consumed only then.  (The reference tests `isinstance(key, dict)`, so a config node that is not a dict
+    subclass always fires there; every `p` of an enabled knob in the published configs is 1.0.)"""
+    return (not isinstance(key, Mapping)) or ("p" not in key) or bool(rng.random() < key["p"])
+
+
+_R_ANGLES = (0.0, math.pi / 2, math.pi, math.pi * 3 / 2)
+
+
+def _draw_rotation(cfg, rng: np.random.Generator) -> np.ndarray:
+    """data_augmentor.py:69-93 / :120-144: axis-aligned or uniform angles times `value`, the reference's rx, ry, rz
+    (its rz is the transpose of build_rotate_mat's), optionally multiplied in a shuffled order."""
+    if cfg["axis_align"]:
+        th = [_R_ANGLES[int(rng.integers(4))] * cfg["value"][i] for i in range(3)]
+    else:
+        th = [(rng.random() * 2 * math.pi - math.pi) * cfg["value"][i] for i in range(3)]
+    rx = np.array([[1, 0, 0], [0, math.cos(th[0]), -math.sin(th[0])], [0, math.sin(th[0]), math.cos(th[0])]])
+    ry = np.array([[math.cos(th[1]), 0, math.sin(th[1])], [0, 1, 0], [-math.sin(th[1]), 0, math.cos(th[1])]])
+    rz = np.array([[math.cos(th[2]), math.sin(th[2]), 0], [-math.sin(th[2]), math.cos(th[2]), 0], [0, 0, 1]])
+    mats = [rx, ry, rz]
+    if cfg.get("shuffle", False):
+        mats = [mats[i] for i in rng.permutation(3)]
+    return mats[0].dot(mats[1]).dot(mats[2])
+
+
+def _draw_translation(cfg, rng: np.random.Generator) -> np.ndarray:
+    return np.array([rng.standard_normal() * cfg["value"][i] for i in range(3)])
+
+
+def draw_aug_params(aug_cfg, split: str, B: int, O: int, rng: np.random.Generator) -> AugParams:
+    """One batch's draws under the reference's `data_aug` schema (any mapping: a dict, an OmegaConf node), with the laws
+    of DataAugmentor.scene_aug / obj_aug (data_augmentor.py:39-154) on `rng`; the reference's global-RNG stream is
+    not reproduced.  Only the augmentors named in `aug_list` run, and none at all on a split other than 'train'.
+    Like the reference, `random_jitter.p` and `accord_to_size` are not read, and `order_shuffle` is not drawn (it
+    only fills obj_order, which _obj_processing_aug never reads)."""
+    a = AugParams()
+    if aug_cfg is None or split != "train":
+        return a
+    for name in aug_cfg["aug_list"]:
+        if name not in aug_cfg:
+            continue
+        cfg = aug_cfg[name]
+        if name == "scene_aug":
+            a.scene_trans, a.scene_scale, a.scene_flip = [None] * B, [None] * B, [None] * B
+            a.scene_rot, a.rgb_delta = [None] * B, [None] * B
+            for b in range(B):
+                c = cfg.get("translation")
+                if _check_key(c) and _check_p(c, rng):
+                    a.scene_trans[b] = _draw_translation(c, rng)
+                c = cfg.get("scaling")
+                if _check_key(c) and _check_p(c, rng):
+                    a.scene_scale[b] = rng.random() * (c["value"][1] - c["value"][0]) + c["value"][0]
+                c = cfg.get("flip")
+                if _check_key(c) and _check_p(c, rng):
+                    m, kind = np.eye(3), int(rng.integers(4))     # x, y, x + y, or none at all
+                    if kind in (0, 2):
+                        m[0][0] *= -1
+                    if kind in (1, 2):
+                        m[1][1] *= -1
+                    a.scene_flip[b] = m
+                c = cfg.get("rotation")
+                if _check_key(c) and _check_p(c, rng):
+                    a.scene_rot[b] = _draw_rotation(c, rng)
+                if _check_key(cfg.get("color_jitter")):
+                    a.rgb_delta[b] = rng.standard_normal(3) * 0.1
+        elif name == "obj_aug":
+            a.obj_trans, a.obj_rot = [[None] * O for _ in range(B)], [[None] * O for _ in range(B)]
+            for b in range(B):
+                for o in range(O):
+                    c = cfg.get("translation")
+                    if _check_key(c) and _check_p(c, rng):
+                        a.obj_trans[b][o] = _draw_translation(c, rng)
+                    c = cfg.get("rotation")
+                    if _check_key(c) and _check_p(c, rng):
+                        a.obj_rot[b][o] = _draw_rotation(c, rng)
+            if _check_key(cfg.get("random_jitter")):
+                a.obj_jitter = [cfg["random_jitter"]["value"]] * B
+            if _check_key(cfg.get("pts_shuffle")):
+                a.pts_shuffle = [True] * B
+        else:
+            raise ValueError(f"draw_aug_params: unknown augmentor {name!r} in aug_list")
+    return a
+
+
 def rot_rows(rot, B: int, O: int, dev):
     """Per-scene rotations -> (matrices (n,3,3) f32 on dev, row_rot (B*O) int32 with -1 = unrotated).
     `rot` is a (B,3,3) tensor/array, or a list with None for scenes build_rotate_mat left unrotated."""
@@ -187,12 +443,15 @@ def rot_rows(rot, B: int, O: int, dev):
             torch.from_numpy(row_rot.reshape(-1)).to(dev))
 
 
-def _algorithmic_bytes(packed: PackedScans, row_obj_host, n_rows: int, num_points: int) -> int:
+def _algorithmic_bytes(packed: PackedScans, row_obj_host, n_rows: int, num_points: int, stream_all: bool = True) -> int:
     """Each object's raw points read once (16-byte records; 15 or 24 B/point as two arrays) + the sampled
     points gathered + the f32 feature rows written.  With the row table already on the device the object
-    sizes of THIS batch are not known on the host without a sync: the mean object size stands in."""
+    sizes of THIS batch are not known on the host without a sync: the mean object size stands in.
+    stream_all=False: the augmented path without scaling, which reads the gathered records only."""
     per_pt = 16 if packed.rgb is None else 12 + 3 * packed.rgb.element_size()
-    if row_obj_host is not None:
+    if not stream_all:
+        k_total = 0
+    elif row_obj_host is not None:
         ids = row_obj_host.reshape(-1).numpy()
         k_total = int(packed.sizes_host[ids[ids >= 0]].sum())
     else:

@@ -46,12 +46,64 @@ def timeit(fn, iters=20, warm=3):
     return s.elapsed_time(e) * 1e3 / iters  # us
 
 
+def bench_objects(batch, dev, rows):
+    """loader-side object processing (gps_obj_processing_post / gps_obj_processing_aug): `batch` scenes x 80 slots x
+    1024 points from HBM-resident raw scans (ScanNet-like object sizes: log-uniform 50..20000 points)"""
+    import numpy as np
+    from sceneverse_amd.data import gpu_objects as G
+    rng = np.random.default_rng(0)
+    packed = G.PackedScans(dev)
+    for s in range(16):
+        n = int(rng.integers(20, 80))
+        ks = np.exp(rng.uniform(np.log(50), np.log(20000), size=n)).astype(np.int64)
+        pts = rng.normal(size=(int(ks.sum()), 3)).astype(np.float32)
+        col = rng.integers(0, 256, size=(int(ks.sum()), 3), dtype=np.uint8)
+        packed.add_scan(f"s{s}", pts, col, np.repeat(np.arange(n), ks), list(range(n)))
+    packed.finalize()
+    slots = G.batch_rows(packed, [f"s{i % 16}" for i in range(batch)], 80)
+    raw = int(packed.sizes_host[slots.reshape(-1).numpy()[slots.reshape(-1).numpy() >= 0]].sum())
+    slots_d = slots.to(dev)
+    # the augmented path (ScanBase._obj_processing_aug): the published data_aug block (one z-rotation per scene, no
+    # pass over the whole object) and every knob on (scaling sums all points; jitter draws 3 normals per point)
+    z = np.array([[0.0, 1, 0], [-1, 0, 0], [0, 0, 1]])
+    pub = G.AugParams(scene_rot=[z] * batch)
+    r = np.random.default_rng(1)
+    knobs = G.AugParams(scene_flip=[np.diag([-1.0, 1, 1])] * batch, scene_scale=[1.05] * batch,
+                        scene_trans=[r.normal(size=3) for _ in range(batch)], scene_rot=[z] * batch,
+                        rgb_delta=[r.normal(size=3) * 0.1 for _ in range(batch)],
+                        obj_trans=[[r.normal(size=3) * 0.1 for _ in range(80)] for _ in range(batch)],
+                        obj_rot=[[z] * 80 for _ in range(batch)], obj_jitter=[0.01] * batch)
+    pub, knobs = pub.to_device(batch, 80, dev), knobs.to_device(batch, 80, dev)   # the upload is not the launch
+    forms = [("obj_processing_post", True, lambda: G.obj_processing_post(packed, slots_d, 1024, seed=1)),
+             ("obj_processing_aug, no augmentation (val)", False, lambda: G.obj_processing_aug(packed, slots_d, 1024, seed=1)),
+             ("obj_processing_aug, published config", False,
+              lambda: G.obj_processing_aug(packed, slots_d, 1024, aug=pub, seed=1)),
+             ("obj_processing_aug, every knob", True,
+              lambda: G.obj_processing_aug(packed, slots_d, 1024, aug=knobs, seed=1))]
+    for name, stream_all, fn in forms:
+        nbytes = G._algorithmic_bytes(packed, slots, slots.numel(), 1024, stream_all=stream_all)
+        us = timeit(fn)
+        row = {"op": f"{name} ({batch}x80 slots, 1024 pts, device sampler)", "us": round(us, 2),
+               "algorithmic_bytes": nbytes, "GBps": round(nbytes / us / 1e3, 1),
+               "frac_8TBps": round(nbytes / us / 1e3 / 8000, 4), "raw_points_per_batch": raw}
+        print(row, flush=True)
+        rows.append(row)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--objects-only", action="store_true", help="time the loader-side object processing alone")
     args = ap.parse_args()
     dev = "cuda"
+    if args.objects_only:
+        rows = []
+        bench_objects(args.batch, dev, rows)
+        if args.json:
+            with open(args.json, "w") as f:
+                json.dump({"batch": args.batch, "rows": rows}, f, indent=1)
+        return
     d = synth_batch(args.batch, seed=42)
     pcs = d["obj_fts"].reshape(-1, 1024, 6).to(dev)
     xyz = pcs[..., :3].contiguous()
@@ -144,29 +196,7 @@ def main():
            "frac_8TBps": round(total_bq_group_bytes / total_bq_group_us / 1e3 / 8000, 4)}
     print(agg)
     rows.append(agg)
-    # loader-side object processing (gps_obj_processing_post): 64 scenes x 80 slots x 1024 points from
-    # HBM-resident raw scans (ScanNet-like object sizes: log-uniform 50..20000 points)
-    import numpy as np
-    from sceneverse_amd.data import gpu_objects as G
-    rng = np.random.default_rng(0)
-    packed = G.PackedScans(dev)
-    for s in range(16):
-        n = int(rng.integers(20, 80))
-        ks = np.exp(rng.uniform(np.log(50), np.log(20000), size=n)).astype(np.int64)
-        pts = rng.normal(size=(int(ks.sum()), 3)).astype(np.float32)
-        col = rng.integers(0, 256, size=(int(ks.sum()), 3), dtype=np.uint8)
-        packed.add_scan(f"s{s}", pts, col, np.repeat(np.arange(n), ks), list(range(n)))
-    packed.finalize()
-    slots = G.batch_rows(packed, [f"s{i % 16}" for i in range(args.batch)], 80)
-    nbytes = G._algorithmic_bytes(packed, slots, slots.numel(), 1024)
-    slots_d = slots.to(dev)
-    us = timeit(lambda: G.obj_processing_post(packed, slots_d, 1024, seed=1))
-    row = {"op": f"obj_processing_post ({args.batch}x80 slots, 1024 pts, device sampler)", "us": round(us, 2),
-           "algorithmic_bytes": nbytes, "GBps": round(nbytes / us / 1e3, 1),
-           "frac_8TBps": round(nbytes / us / 1e3 / 8000, 4),
-           "raw_points_per_batch": int(packed.sizes_host[slots.reshape(-1).numpy()[slots.reshape(-1).numpy() >= 0]].sum())}
-    print(row, flush=True)
-    rows.append(row)
+    bench_objects(args.batch, dev, rows)
     # bias-gradient column sums (gps_colsum_bf16) next to torch's reduction of the same matrix
     from sceneverse_amd.common import colsum as WS
     for T, N in ((19200, 3072), (19200, 768), (8320, 2048), (5120, 2376)):
