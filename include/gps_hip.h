@@ -619,6 +619,59 @@ GPS_API int gps_obj_processing_aug(int n_rows, int n_points, const float *xyz, c
                                    float *obj_fts, float *obj_locs, float *obj_boxes, uint8_t *obj_masks,
                                    gps_stream_t stream);
 
+/* ---- ScanRefer targets for predicted proposals: boxes, IoU flags, metrics ------------------------------
+ * Replaces, for a `pc_type: 'pred'` (and 'gt') ScanRefer batch, what ScanBase._load_scan / _getitem_refer derive
+ * from 3-D box IoU on the loader workers (data/datasets/base.py:105-141, :348-417, :453-454, :478-483), the padding
+ * of data/datasets/dataset_wrapper.py:164-191, and ScanReferEval.batch_metrics (evaluator/scanrefer_eval.py:14-87).
+ *
+ * gps_obj_boxes: convert_pc_to_box (data/data_utils.py:63-72) of EVERY object of the resident scans in one pass.
+ *   xyz: the points of gps_obj_processing_post -- `records` != 0: N 16-byte records (16-byte aligned), else (N,3) f32;
+ *   n_points = N.  work (n_work, 3) int64, built by the host from the object sizes: {object, first point (index into
+ *   xyz), count} with 1 <= count <= GPS_OBJ_BOXES_CHUNK; the chunks of an object cover its CSR segment once.  An
+ *   entry that leaves the arrays (object >= n_objects, first + count > n_points, count out of range) is skipped.
+ *   workspace: 6 * n_objects uint32, set to the identities by the call itself (no initialisation needed).
+ *   boxes (n_objects, 6) float64 = [(min + max) / 2, max - min]: min / max are exact in float32, centre and size are
+ *   float64 operations on them, i.e. bit-equal to numpy on the loader's float64 rows.  Chunk results are combined
+ *   with integer atomic min / max on an order-preserving encoding of the float32 bits, so the result does not depend
+ *   on the chunking or on the run.  -inf / +inf are ordinary values (-0 sorts below +0); a NaN coordinate makes that
+ *   coordinate's centre and size NaN (as np.min / np.max do), and so does an object no chunk covers.
+ *   n_objects == 0: GPS_OK, nothing launched.
+ *
+ * gps_refer_targets: one launch per batch.  O <= GPS_REFER_MAX_OBJ (GPS_ERR_UNSUPPORTED above), B == 0: GPS_OK.
+ *   boxes (n_objects, 6) float64 and labels (n_objects) int32 per resident object; row_obj (B, O) int32 global object
+ *   ids, < 0 (or >= n_objects) = padding slot, the real slots a prefix of length n_b; tgt_obj (B) int32 global id of
+ *   the referred ANNOTATED object; scan_range (B, 2) int32 [first, last) global ids of its scan's annotated objects
+ *   in scan order; mode 0 = 'pred', 1 = 'gt' (anything else GPS_ERR_INVALID_ARGUMENT).
+ *   Outputs: iou25, iou50 (B, O) int64 0/1 (the reference's n_b + 1 entries padded with 0 to O), tgt_id (B) int64,
+ *   obj_labels (B, O) int64 with -100 in the padding slots.
+ *   'pred': iou25/50[b][i] = IoU(proposal in slot i, referred object) >= 0.25 / 0.5; tgt_id[b] = the LARGEST such i
+ *   at 0.25, or n_b when there is none; obj_labels[b][i] = label of the FIRST annotated object j of the scan with
+ *   IoU(j, i) >= 0.25, else the proposal's own label.   'gt': the flags are one-hot where row_obj == tgt_obj,
+ *   tgt_id is that slot (n_b when absent), labels are copied.
+ *   Arithmetic, all float64 without contraction: box lo = c + (-(s / 2)), hi = c + s / 2; inter = max(xB - xA, 0) *
+ *   max(yB - yA, 0) * max(zB - zA, 0) left to right; vol = ((hx - lx) * (hy - ly)) * (hz - lz); iou = inter /
+ *   (((v1 + v2) - inter) + 1e-8) -- box3d_iou (data/data_utils.py:212-234) on construct_bbox_corners' corners bit
+ *   for bit when the scans store integer colours (the loader's rows are float64 then).  With float32-stored colours
+ *   the reference computes the same quantities in float32; this entry stays float64 and is no parity target there.
+ *
+ * gps_refer_metrics: ADDS one batch's counts to counters (8) int64: [0] items, [1] is_multiple items, [2] iou25 hits,
+ *   [3] iou50 hits, [4] iou25 hits among multiple, [5] iou50 hits among multiple, [6] arg-max == tgt_id, [7] spare
+ *   (never written).  og3d_logits (B, O) f32 or (logits_bf16 != 0) bf16 with row pitch ld >= O elements; iou25 / iou50
+ *   (B, O) int64, tgt_id (B) int64, is_multiple (B) u8.  The arg-max follows torch.argmax: the first index of the
+ *   maximum, NaN is the greatest value (the first NaN wins), a row of -inf gives 0.  Integer atomics only: the counts
+ *   do not depend on order.  The caller zeroes the counters when a new evaluation starts.  B == 0: GPS_OK. */
+#define GPS_OBJ_BOXES_CHUNK 4096
+#define GPS_REFER_MAX_OBJ 512
+GPS_API int gps_obj_boxes(int n_objects, long long n_points, int n_work, const float *xyz, int records,
+                          const int64_t *work, uint32_t *workspace, double *boxes, gps_stream_t stream);
+GPS_API int gps_refer_targets(int B, int O, int n_objects, int mode, const double *boxes, const int32_t *labels,
+                              const int32_t *row_obj, const int32_t *tgt_obj, const int32_t *scan_range,
+                              int64_t *iou25, int64_t *iou50, int64_t *tgt_id, int64_t *obj_labels,
+                              gps_stream_t stream);
+GPS_API int gps_refer_metrics(int B, int O, const void *og3d_logits, long long ld, int logits_bf16,
+                              const int64_t *iou25, const int64_t *iou50, const int64_t *tgt_id,
+                              const uint8_t *is_multiple, int64_t *counters, gps_stream_t stream);
+
 /* ---- bias gradients: column sums of a bf16 matrix ---------------------------------------------------
  * Replaces the `dY.sum(0)` autograd derives for the bias of every nn.Linear in the transformer stacks
  * (modules/layers/transformers.py:115-154, 285-316; HF BertLayer behind modules/language/bert.py:21-26).

@@ -113,6 +113,9 @@ SIGNATURES = {
                                 _vp, _vp],
     "gps_obj_processing_aug": [_i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, ctypes.c_ulonglong, _vp, _vp, _i,
                                _vp, _vp, _vp, _vp, _vp],
+    "gps_obj_boxes": [_i, ctypes.c_longlong, _i, _vp, _i, _vp, _vp, _vp, _vp],
+    "gps_refer_targets": [_i, _i, _i, _i] + [_vp] * 10,
+    "gps_refer_metrics": [_i, _i, _vp, ctypes.c_longlong, _i] + [_vp] * 6,
     "gps_embedding_grad_scratch_ints": [_i, _i, _i],
     "gps_embedding_grad": [_i, _i, _i, _vp, _vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, _vp],
     "gps_loc_embed_partial_rows": [_i],

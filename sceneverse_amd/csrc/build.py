@@ -25,6 +25,7 @@ SOURCES = [
     ("gps_qa.hip", []),
     ("gps_layernorm.hip", []),
     ("gps_objects.hip", []),
+    ("gps_refer.hip", ["-ffp-contract=off"]),
     ("gps_reduce.hip", []),
     ("gps_embedding.hip", []),
     ("gps_bert_embed.hip", []),

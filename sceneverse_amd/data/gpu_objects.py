@@ -7,6 +7,8 @@ Reference (what this replaces on the data-loader workers):
     ScanBase._obj_processing_aug   data/datasets/base.py:742-776  the branch of every config with a `data_aug:` block
     DataAugmentor                  data/datasets/data_augmentor.py  its draws (:39-154) and their application (:156-215)
     dataset wrapper padding        data/datasets/dataset_wrapper.py:62-70  pad to max_obj_len, obj_masks
+    ScanBase._getitem_refer        data/datasets/base.py:348-417  `pc_type: 'pred'`: predicted proposals (loaded at
+                                                                  :115-141), labels / flags / target id by box IoU
 
 MI355X form: every scan is uploaded ONCE in its raw on-disk precision (xyz f32 + rgb u8, packed as
 16-byte records, instead of the loader's 48 B/point float64 rows), points regrouped so that each kept instance is
@@ -41,16 +43,23 @@ class PackedScans:
         self._rgb: List[np.ndarray] = []
         self._sizes: List[int] = []
         self._scan_objs: Dict[str, range] = {}
+        self._scan_props: Dict[str, range] = {}
         self._inst_ids: Dict[str, list] = {}
+        self._labels: List[int] = []
         self.xyz = self.rgb = self.obj_offsets = None
+        self.labels = self.boxes = None
         self.sizes_host: Optional[np.ndarray] = None
 
     def add_scan(self, scan_id: str, points: np.ndarray, colors: np.ndarray, instance_labels: np.ndarray,
-                 inst_ids: Sequence[int]) -> None:
+                 inst_ids: Sequence[int], inst_labels: Optional[Sequence[int]] = None) -> None:
         """points (N,3) float32, colors (N,3) uint8 or float32 in 0..255 (the `.pth` contents of
         base.py:70-73), instance_labels (N,), inst_ids: the instances the loader keeps, in its order
-        (base.py:82-89; instances without points are skipped exactly like `np.sum(mask) == 0`)."""
+        (base.py:82-89; instances without points are skipped exactly like `np.sum(mask) == 0`).
+        inst_labels: optionally the class of each entry of inst_ids (base.py:90) -> the per-object `labels` array;
+        objects of a scan added without it carry -100."""
         assert self.xyz is None, "finalize() was already called"
+        if inst_labels is not None and len(inst_labels) != len(inst_ids):
+            raise ValueError("inst_labels must give one label per entry of inst_ids")
         points = np.ascontiguousarray(points, dtype=np.float32)
         if colors.dtype != np.uint8:
             colors = np.ascontiguousarray(colors, dtype=np.float32)
@@ -58,16 +67,48 @@ class PackedScans:
             raise ValueError("all scans must store colours in the same dtype")
         first = len(self._sizes)
         kept = []
-        for inst in inst_ids:
+        for n, inst in enumerate(inst_ids):
             sel = np.flatnonzero(instance_labels == inst)
             if sel.size == 0:
                 continue
             self._xyz.append(points[sel])
             self._rgb.append(np.ascontiguousarray(colors[sel]))
             self._sizes.append(int(sel.size))
+            self._labels.append(-100 if inst_labels is None else int(inst_labels[n]))
             kept.append(inst)
         self._scan_objs[scan_id] = range(first, len(self._sizes))
         self._inst_ids[scan_id] = kept
+
+    def add_proposals(self, scan_id: str, points: np.ndarray, colors: np.ndarray, masks: np.ndarray,
+                      labels: Sequence[int]) -> None:
+        """The predicted instance masks of a scan (base.py:115-141 after its `[:50]` cut, which is the caller's): masks
+        (n_prop, N) bool / 0-1 over the scan's points, labels (n_prop,).  Every proposal with at least one point becomes
+        one more object of the packed arrays, its points in `pcds[mask == 1]` order; masks may overlap (a point is then
+        stored once per proposal) and empty ones are skipped like `pcds[mask == 1].shape[0] > 0`.  Call it after
+        add_scan for the same scan (same points and colors) and before finalize()."""
+        assert self.xyz is None, "finalize() was already called"
+        if scan_id not in self._scan_objs:
+            raise KeyError(f"add_proposals: add_scan({scan_id!r}) comes first")
+        if scan_id in self._scan_props:
+            raise ValueError(f"add_proposals: scan {scan_id!r} already has its proposals")
+        points = np.ascontiguousarray(points, dtype=np.float32)
+        if colors.dtype != np.uint8:
+            colors = np.ascontiguousarray(colors, dtype=np.float32)
+        if self._rgb and self._rgb[0].dtype != colors.dtype:
+            raise ValueError("all scans must store colours in the same dtype")
+        masks = np.asarray(masks).reshape(-1, points.shape[0])
+        if len(labels) != masks.shape[0]:
+            raise ValueError("add_proposals: one label per mask")
+        first = len(self._sizes)
+        for mask, label in zip(masks, labels):
+            sel = np.flatnonzero(mask == 1)
+            if sel.size == 0:
+                continue
+            self._xyz.append(points[sel])
+            self._rgb.append(np.ascontiguousarray(colors[sel]))
+            self._sizes.append(int(sel.size))
+            self._labels.append(int(label))
+        self._scan_props[scan_id] = range(first, len(self._sizes))
 
     def finalize(self) -> "PackedScans":
         sizes = np.asarray(self._sizes, dtype=np.int64)
@@ -85,12 +126,19 @@ class PackedScans:
             self.records = False
             self.xyz, self.rgb = torch.from_numpy(xyz).to(self.device), torch.from_numpy(rgb).to(self.device)
         self.obj_offsets = torch.from_numpy(off).to(self.device)
+        self.labels = torch.from_numpy(np.asarray(self._labels, dtype=np.int32)).to(self.device)
         self._xyz, self._rgb = [], []
+        if self.device.type == "cuda":             # the boxes are a device product: no CPU path
+            self.boxes = obj_boxes(self)
         return self
 
     def scan_objects(self, scan_id: str) -> range:
-        """Global object ids of a scan, in the loader's object order."""
+        """Global object ids of a scan's annotated objects, in the loader's object order."""
         return self._scan_objs[scan_id]
+
+    def scan_proposals(self, scan_id: str) -> range:
+        """Global object ids of a scan's proposals (add_proposals), in mask order without the empty ones."""
+        return self._scan_props[scan_id]
 
     def scan_inst_ids(self, scan_id: str) -> list:
         return self._inst_ids[scan_id]
@@ -101,12 +149,13 @@ class PackedScans:
 
 
 def batch_rows(packed: PackedScans, scan_ids: Sequence[str], max_obj_len: int,
-               obj_select: Optional[Sequence[Sequence[int]]] = None) -> torch.Tensor:
+               obj_select: Optional[Sequence[Sequence[int]]] = None, proposals: bool = False) -> torch.Tensor:
     """(B, max_obj_len) int32 table of global object ids, -1 = padding slot.  obj_select[b] optionally
-    lists scene-local object positions (the loader's selected_obj_idxs, base.py:236-246)."""
+    lists scene-local object positions (the loader's selected_obj_idxs, base.py:236-246).  proposals=True fills
+    the rows from the scans' proposals (`pc_type: 'pred'`) instead of their annotated objects."""
     rows = np.full((len(scan_ids), max_obj_len), -1, dtype=np.int32)
     for b, sid in enumerate(scan_ids):
-        objs = list(packed.scan_objects(sid))
+        objs = list(packed.scan_proposals(sid) if proposals else packed.scan_objects(sid))
         if obj_select is not None:
             objs = [objs[i] for i in obj_select[b]]
         if len(objs) > max_obj_len:
@@ -172,6 +221,105 @@ def obj_processing_post(packed: PackedScans, row_obj: torch.Tensor, num_points: 
     res = {"obj_fts": fts, "obj_locs": locs, "obj_masks": masks if masks.dtype == torch.bool else masks.bool()}
     if need_boxes:
         res["obj_boxes"] = boxes
+    return res
+
+
+# ---- ScanRefer targets: boxes of every object, IoU flags per batch ---------------------------------------------
+BOXES_CHUNK = 4096                               # GPS_OBJ_BOXES_CHUNK of include/gps_hip.h
+REFER_MAX_OBJ = 512                              # GPS_REFER_MAX_OBJ
+_REFER_OUT = (("tgt_object_id_iou25", None), ("tgt_object_id_iou50", None), ("tgt_object_id", 1), ("obj_labels", None))
+
+
+def boxes_work_list(sizes: np.ndarray, chunk: int = BOXES_CHUNK) -> np.ndarray:
+    """(n_work, 3) int64 {object, first point, count <= chunk}: every object's CSR segment cut into bounded chunks, so
+    that one launch is balanced whatever the largest object is (a floor has several hundred thousand points)."""
+    sizes = np.asarray(sizes, dtype=np.int64)
+    off = np.zeros(len(sizes) + 1, dtype=np.int64)
+    np.cumsum(sizes, out=off[1:])
+    n_chunks = (sizes + chunk - 1) // chunk
+    obj = np.repeat(np.arange(len(sizes), dtype=np.int64), n_chunks)
+    start = np.zeros(len(sizes) + 1, dtype=np.int64)
+    np.cumsum(n_chunks, out=start[1:])
+    k = np.arange(obj.shape[0], dtype=np.int64) - start[obj]
+    work = np.empty((obj.shape[0], 3), dtype=np.int64)
+    work[:, 0] = obj
+    work[:, 1] = off[obj] + k * chunk
+    work[:, 2] = np.minimum(sizes[obj] - k * chunk, chunk)
+    return work
+
+
+def obj_boxes(packed: PackedScans) -> torch.Tensor:
+    """convert_pc_to_box (data/data_utils.py:63-72) of every packed object, annotated and proposal, in one pass:
+    (n_objects, 6) float64 [centre, size], bit-equal to numpy on the loader's float64 rows.  finalize() calls it once
+    and keeps the result as `packed.boxes`."""
+    if packed.xyz is None:
+        raise RuntimeError("PackedScans.finalize() has not been called")
+    dev = packed.xyz.device
+    if dev.type != "cuda":
+        raise RuntimeError("obj_boxes runs on libgps_hip.so: scenes must live on a GPU (no CPU path)")
+    n = packed.n_objects
+    boxes = torch.empty((n, 6), dtype=torch.float64, device=dev)
+    if n == 0:
+        return boxes
+    work = torch.from_numpy(boxes_work_list(packed.sizes_host)).to(dev)
+    ws = torch.empty(n * 6, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        st = _native.load().gps_obj_boxes(n, int(packed.xyz.shape[0]), int(work.shape[0]), packed.xyz.data_ptr(),
+                                          int(packed.rgb is None), work.data_ptr(), ws.data_ptr(), boxes.data_ptr(),
+                                          torch.cuda.current_stream(dev).cuda_stream)
+    _native.check(st, "obj_boxes")
+    return boxes
+
+
+def refer_targets(packed: PackedScans, row_obj: torch.Tensor, tgt_obj, scan_ids: Sequence[str], pc_type: str = "pred",
+                  out: Optional[dict] = None) -> dict:
+    """The targets ScanBase._getitem_refer derives from box IoU (base.py:348-417, :453-454, :478-483) in the layouts the
+    dataset wrapper hands to the model (dataset_wrapper.py:164-191), for a whole batch in one launch and without a host
+    sync: tgt_object_id_iou25 / tgt_object_id_iou50 (B,O) int64, tgt_object_id (B,1) int64, obj_labels (B,O) int64 with
+    -100 in the padding slots.
+
+    row_obj (B,O) int32: batch_rows(..., proposals=True) for pc_type 'pred', batch_rows(...) for 'gt'.
+    tgt_obj: per item the position of the referred object among its scan's annotated objects (`obj_ids.index(
+    tgt_object_instance)`, base.py:398), a sequence or a tensor on any device.  scan_ids: the items' scans.
+    out: optional dict of preallocated contiguous tensors of those four names, shapes and dtypes, written IN PLACE.
+    The reference's flag vectors have n_b + 1 entries, so a scene that fills all O slots cannot be padded there
+    (pad_tensors asserts); a row table on the host is checked for that here (ValueError), one on the device is not.
+    Integer-stored colours: bit-equal flags; float32-stored colours: the float64 form still (the reference's float32
+    boxes are no parity target).  `is_multiple` / `is_hard` stay dictionary look-ups of the caller."""
+    if packed.xyz is None:
+        raise RuntimeError("PackedScans.finalize() has not been called")
+    if pc_type not in ("pred", "gt"):
+        raise ValueError(f"refer_targets: pc_type {pc_type!r} is neither 'pred' nor 'gt'")
+    B, O = row_obj.shape
+    if len(scan_ids) != B:
+        raise ValueError(f"refer_targets: {len(scan_ids)} scan ids for {B} rows")
+    if O > REFER_MAX_OBJ:
+        raise ValueError(f"refer_targets: {O} object slots > {REFER_MAX_OBJ}")
+    if row_obj.device.type == "cpu" and B and bool((row_obj[:, -1] >= 0).any()):
+        raise ValueError("refer_targets: a scene fills all object slots; the targets need max_obj_len >= n_objects + 1")
+    dev = packed.xyz.device
+    if dev.type != "cuda":
+        raise RuntimeError("refer_targets runs on libgps_hip.so: scenes must live on a GPU (no CPU path)")
+    row_obj = row_obj.to(device=dev, dtype=torch.int32).contiguous()
+    ranges = np.asarray([[r.start, r.stop] for r in (packed.scan_objects(s) for s in scan_ids)],
+                        dtype=np.int32).reshape(B, 2)
+    ranges = torch.from_numpy(ranges).to(dev)
+    tgt = torch.as_tensor(tgt_obj).reshape(B).to(device=dev, dtype=torch.int32) + ranges[:, 0]
+    shapes = {name: (B, w if w is not None else O) for name, w in _REFER_OUT}
+    if out is not None:
+        res = {name: out[name] for name, _ in _REFER_OUT}
+        if not all(t.shape == shapes[n] and t.dtype == torch.int64 and t.is_contiguous() and t.device == dev
+                   for n, t in res.items()):
+            raise ValueError("refer_targets: `out` tensors must be contiguous int64 (B,O) / (B,1) on the scans' GPU")
+    else:
+        res = {name: torch.empty(shapes[name], dtype=torch.int64, device=dev) for name, _ in _REFER_OUT}
+    with torch.cuda.device(dev):
+        st = _native.load().gps_refer_targets(
+            B, O, packed.n_objects, int(pc_type == "gt"), packed.boxes.data_ptr(), packed.labels.data_ptr(),
+            row_obj.data_ptr(), tgt.data_ptr(), ranges.data_ptr(), res["tgt_object_id_iou25"].data_ptr(),
+            res["tgt_object_id_iou50"].data_ptr(), res["tgt_object_id"].data_ptr(), res["obj_labels"].data_ptr(),
+            torch.cuda.current_stream(dev).cuda_stream)
+    _native.check(st, "refer_targets")
     return res
 
 

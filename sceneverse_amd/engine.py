@@ -756,6 +756,64 @@ def scanrefer_accuracy(og3d_logits: torch.Tensor, iou25_onehot: torch.Tensor,
     return {"og_acc_iou25": hit25.sum().item() / n, "og_acc_iou50": hit50.sum().item() / n}
 
 
+class ScanReferCounter:
+    """ScanReferEval.batch_metrics (evaluator/scanrefer_eval.py:14-87) as counts that stay on the device: `update`
+    is one launch of libgps_hip.so (gps_refer_metrics) that adds a batch into 8 int64 counters -- no `.item()`, so an
+    evaluation loop has no per-batch host sync and an update can be captured in a graph.  `result()` is the one sync.
+
+    batch: `tgt_object_id_iou25`, `tgt_object_id_iou50` (B,O) int64, `tgt_object_id` (B,1) or (B,) int64 and
+    `is_multiple` (B,) bool / uint8, all on the logits' GPU (data.gpu_objects.refer_targets builds the first three)."""
+    _COUNTS = ("total", "multiple", "iou25", "iou50", "iou25_multiple", "iou50_multiple", "og_acc")
+
+    def __init__(self, device: torch.device | str = "cuda"):
+        self.counts = torch.zeros(8, dtype=torch.int64, device=device)
+
+    def reset(self) -> None:
+        self.counts.zero_()
+
+    def update(self, og3d_logits: torch.Tensor, batch: dict) -> None:
+        from . import _native
+        dev = self.counts.device
+        if og3d_logits.device.type != "cuda" or dev.type != "cuda":
+            raise RuntimeError("ScanReferCounter runs on libgps_hip.so: logits and counters must live on a GPU (no CPU path)")
+        if og3d_logits.dim() != 2 or og3d_logits.dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError("ScanReferCounter: og3d_logits must be (B,O) float32 or bfloat16")
+        B, O = og3d_logits.shape
+        if og3d_logits.stride(1) != 1 or (B > 1 and og3d_logits.stride(0) < O):
+            og3d_logits = og3d_logits.contiguous()
+        iou25, iou50 = batch["tgt_object_id_iou25"], batch["tgt_object_id_iou50"]
+        tgt, mult = batch["tgt_object_id"].reshape(-1), batch["is_multiple"].reshape(-1)
+        if mult.dtype == torch.bool:
+            mult = mult.view(torch.uint8)
+        for name, t, shape, dtype in (("tgt_object_id_iou25", iou25, (B, O), torch.int64),
+                                      ("tgt_object_id_iou50", iou50, (B, O), torch.int64),
+                                      ("tgt_object_id", tgt, (B,), torch.int64), ("is_multiple", mult, (B,), torch.uint8)):
+            if tuple(t.shape) != shape or t.dtype != dtype or t.device != og3d_logits.device or not t.is_contiguous():
+                raise ValueError(f"ScanReferCounter: {name} must be contiguous {dtype} {shape} on the logits' GPU")
+        if og3d_logits.device != dev:
+            raise ValueError("ScanReferCounter: the logits live on another GPU than the counters")
+        with torch.cuda.device(dev):
+            st = _native.load().gps_refer_metrics(
+                B, O, og3d_logits.data_ptr(), og3d_logits.stride(0) if B > 1 else O,
+                int(og3d_logits.dtype == torch.bfloat16), iou25.data_ptr(), iou50.data_ptr(), tgt.data_ptr(),
+                mult.data_ptr(), self.counts.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        _native.check(st, "refer_metrics")
+
+    def result(self, include_count: bool = False) -> dict:
+        """The reference's keys; ratios hits / max(count, 1), or with include_count the (hits, count) pairs."""
+        c = dict(zip(self._COUNTS, self.counts.tolist()))
+        unique = c["total"] - c["multiple"]
+        pairs = {"og_acc_iou25": (c["iou25"], c["total"]), "og_acc_iou50": (c["iou50"], c["total"]),
+                 "og_acc_iou25_unique": (c["iou25"] - c["iou25_multiple"], unique),
+                 "og_acc_iou50_unique": (c["iou50"] - c["iou50_multiple"], unique),
+                 "og_acc_iou25_multiple": (c["iou25_multiple"], c["multiple"]),
+                 "og_acc_iou50_multiple": (c["iou50_multiple"], c["multiple"]),
+                 "og_acc": (c["og_acc"], c["total"])}
+        if include_count:
+            return pairs
+        return {k: h / max(n, 1) for k, (h, n) in pairs.items()}
+
+
 def _answer_hits(answer_scores: torch.Tensor, answer_label: torch.Tensor, k: int = 10):
     """(hit@1, hit@k) per row as bool vectors: the label entry at the arg-max answer / at any of the top-k answers is 1."""
     top1 = answer_scores.argmax(dim=-1, keepdim=True)
