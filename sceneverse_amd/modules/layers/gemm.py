@@ -11,6 +11,10 @@ as explicit autograd functions (no global F.linear patching):
     packed_linear(x, [(W_i, b_i), ...])           y = x [W_0; W_1; ...]^T + [b_0; b_1; ...]   (one GEMM)
     ffn(x, W1, b1, W2, b2, act, p_drop, training) y = dropout(act(x W1^T + b1)) W2^T + b2
 
+The forward and the backward of the packed Linear and of the FFN are each written once, for one stack's operands, as a
+recipe that yields its GEMM products stage by stage (`_linear_forward` ... `_ffn_backward`); `_LinearFn` / `_FFNFn` run the
+recipes of one stack, or of two independent stacks in step with each stage's products in one launch (`drive_pair`).
+
 Parameters stay fp32 masters (checkpoint- and optimizer-compatible with the reference); the GEMMs read a
 persistent bf16 SHADOW of every weight that is refreshed only when the master changed (`_version`) -- or
 written by the optimizer kernel itself (optim/fused_adamw.py) -- instead of autocast's per-call casts.
@@ -780,72 +784,239 @@ def _as_rows16(x: torch.Tensor) -> torch.Tensor:
     return x2
 
 
-# forward results computed ahead of the autograd node that owns them (`_twin_*_forward_only`: the two stacks' forward
-# products leave paired, their backward passes stay separate nodes): id(input tensor) -> what the node's forward would compute
-_PRECOMPUTED = {}
+# ---- Linear and FFN: one recipe per computation, one runner, one autograd node for one or two sides -------------------
+# A SIDE is one stack's operands of a packed Linear, (x, rows_dev, weights, biases), or of an FFN, the same with
+# weights = (W1, W2), biases = (b1, b2) and (act, p_drop, seed_dev) behind them.  The recipes below state the forward and
+# the backward of either computation ONCE, for one side, as generators that PREPARE their NT / NN products and yield them
+# stage by stage; `_run` advances the recipes of one or two sides in step and sends each stage's products out together.
+# `_LinearFn` / `_FFNFn` serve a list of sides: one side is the plain Linear / FFN, two sides are a pair of `drive_pair`.
+def _run(recipes) -> list:
+    """Advance the recipes of 1 or 2 sides in step: each stage's products leave through `_launch_together` (a lone
+    product: `_launch`); a side without work at a stage contributes nothing.  -> what each recipe returned."""
+    results, live = [None] * len(recipes), list(enumerate(recipes))
+    while live:
+        products, ahead = [], []
+        for i, recipe in live:
+            try:
+                products.append(next(recipe))
+                ahead.append((i, recipe))
+            except StopIteration as stop:
+                results[i] = stop.value
+        if products:
+            _launch_together(products)
+        live = ahead
+    return results
+
+
+class _Slots:
+    """Where one side's arguments sit in `Fn.apply(ns, ahead, *arguments of every side)`: x, rows_dev, n weights, n biases,
+    `extra` scalars.  The ONE description of that layout: `forward` picks its arguments by it, `backward` reads
+    needs_input_grad and places the gradients by it, the call site flattens its sides by it."""
+    __slots__ = ("x", "rows_dev", "weights", "biases", "extra")
+
+    def __init__(self, at: int, n: int, extra: int):
+        self.x, self.rows_dev = at, at + 1
+        self.weights = slice(at + 2, at + 2 + n)
+        self.biases = slice(self.weights.stop, self.weights.stop + n)
+        self.extra = slice(self.biases.stop, self.biases.stop + extra)
+
+    @staticmethod
+    def of(ns, extra: int) -> list:
+        out, at = [], 2                                      # behind ns, ahead
+        for n in ns:
+            out.append(_Slots(at, n, extra))
+            at = out[-1].extra.stop
+        return out
+
+    def pick(self, args) -> tuple:
+        return (args[self.x], args[self.rows_dev], args[self.weights], args[self.biases], *args[self.extra])
+
+    @staticmethod
+    def flat(sides) -> list:
+        return [a for x, rows_dev, weights, biases, *extra in sides for a in (x, rows_dev, *weights, *biases, *extra)]
+
+
+def _all_needed(biases, need_ws, need_bs) -> bool:
+    """Every weight and every present bias needs its gradient: the condition of `_wgrad_to_params`."""
+    return all(need_ws) and all(b is None or g for b, g in zip(biases, need_bs))
+
+
+def _wgrad_blocks(dy16, x16, weights, biases, need_ws, need_bs, rows_dev):
+    """`linear_wgrad` of a packed Linear, cut back into its blocks -> (dws, dbs), None where no gradient is needed."""
+    dw, db = linear_wgrad(dy16, x16, want_bias=any(need_bs), rows_dev=rows_dev)
+    dws, dbs, r = [], [], 0
+    for w, b, need_w, need_b in zip(weights, biases, need_ws, need_bs):
+        n = w.shape[0]
+        dws.append(dw[r:r + n] if need_w else None)
+        dbs.append(db[r:r + n] if b is not None and need_b else None)
+        r += n
+    return dws, dbs
+
+
+def _dx_out(dx, shape, dtype):
+    dx = dx.view(shape)
+    return dx if dx.dtype == dtype else dx.to(dtype)
+
+
+def _linear_forward(x, rows_dev, weights, biases):
+    """-> (tensors saved for backward, y, notes for backward)"""
+    w16, b32 = shadow_of(weights, biases)
+    x16 = _as_rows16(x)
+    q, y, _ = _forward_product(x16, w16, b32, rows_dev=rows_dev)
+    yield q
+    return (x16, w16), y, ()
+
+
+def _linear_backward(dy, saved, x_shape, x_dtype, rows_dev, weights, biases, need_x, need_ws, need_bs):
+    """-> (dx, dws, dbs).  On the stream: a deferred weight gradient, the input gradient, a weight gradient autograd gets."""
+    x16, w16 = saved
+    dy16 = _as_rows16(dy)
+    dx, dws, dbs = None, [None] * len(weights), [None] * len(weights)
+    deferred = _all_needed(biases, need_ws, need_bs) and \
+        _wgrad_to_params(dy16, x16, weights, biases, [w.shape[0] for w in weights], rows_dev)      # side stream, first
+    if need_x:
+        q, dx = _dgrad_product(dy16, w16, rows_dev=rows_dev)
+        yield q
+        dx = _dx_out(dx, x_shape, x_dtype)
+    if (any(need_ws) or any(need_bs)) and not deferred:
+        dws, dbs = _wgrad_blocks(dy16, x16, weights, biases, need_ws, need_bs, rows_dev)
+    return dx, dws, dbs
+
+
+_GELU_FACTOR = True          # False: save the pre-activation and recompute gelu' and the mask in the backward epilogue (A/B, tests)
+
+
+def set_gelu_factor(flag: bool) -> None:
+    global _GELU_FACTOR
+    _GELU_FACTOR = bool(flag)
+
+
+def _ffn_forward(x, rows_dev, weights, biases, act, p_drop, seed_dev):
+    """-> (tensors saved for backward, y, notes for backward)"""
+    (w1, w2), (b1, b2) = weights, biases
+    w1_16, b1_32 = shadow_of((w1,), (b1,))
+    w2_16, b2_32 = shadow_of((w2,), (b2,))
+    x16 = _as_rows16(x)
+    # gelu: the forward epilogue saves gelu'(pre) x dropout-mask / (1 - p) (one multiply per element in the backward
+    # epilogue instead of the erf terms and the mask hash: gps_gemm.hip EPI_BIAS_GELU_FACTOR / EPI_MUL_AUX)
+    factor = act == "gelu" and _GELU_FACTOR
+    q, h, pre = _forward_product(x16, w1_16, b1_32, act=act, p_drop=p_drop, seed_dev=seed_dev,
+                                 want_pre="factor" if factor else True, rows_dev=rows_dev)
+    yield q
+    q, y, _ = _forward_product(h, w2_16, b2_32, rows_dev=rows_dev)
+    yield q
+    return (x16, w1_16, w2_16, h, pre, seed_dev), y, (act, float(p_drop), factor)
+
+
+def _ffn_backward(dy, saved, x_shape, x_dtype, act, p_drop, factor, rows_dev, weights, biases, need_x, need_ws, need_bs):
+    """-> (dx, dws, dbs).  Either weight gradient is issued before the input-gradient product that follows it."""
+    x16, w1_16, w2_16, h, pre, seed_dev = saved
+    (w1, w2), (b1, b2) = weights, biases
+    dy16 = _as_rows16(dy)
+    all_w = _all_needed(biases, need_ws, need_bs)
+
+    def wgrad(g16, a16, w, b):
+        if all_w and _wgrad_to_params(g16, a16, (w,), (b,), (w.shape[0],), rows_dev):
+            return None, None
+        # not all needed: BOTH weight gradients are computed whatever the need flags say (ADVICE.md, wasteful, kept)
+        (dw,), (db,) = _wgrad_blocks(g16, a16, (w,), (b,), (True,), (b is not None,), rows_dev)
+        return dw, db
+
+    dw2, db2 = wgrad(dy16, h, w2, b2)
+    q, dpre = _dgrad_product(dy16, w2_16, act="factor" if factor else act, aux=pre if act == "gelu" else h, p_drop=p_drop,
+                             seed_dev=seed_dev, rows_dev=rows_dev)
+    yield q
+    dw1, db1 = wgrad(dpre, x16, w1, b1)
+    dx = None
+    if need_x:
+        q, dx = _dgrad_product(dpre, w1_16, rows_dev=rows_dev)
+        yield q
+        dx = _dx_out(dx, x_shape, x_dtype)
+    return dx, [dw1, dw2], [db1, db2]
+
+
+def _node_forward(ctx, fn, *args):
+    """`forward` of both nodes, args = (ns, ahead, *arguments of every side): run every side's forward recipe -- or take
+    over its result, computed `ahead` -- and keep what the backward recipes need."""
+    slots, ahead = _Slots.of(args[0], fn.EXTRA), args[1]
+    sides = [s.pick(args) for s in slots]
+    if len(sides) > 1:
+        ctx.set_materialize_grads(False)                     # a backward call may bring one side's gradient only
+    states = ahead if ahead is not None else _run([fn.recipe(*sd) for sd in sides])
+    ctx.save_for_backward(*[t for saved, _, _ in states for t in saved])
+    ctx.slots = slots
+    ctx.meta = [(len(saved), x.shape, x.dtype, *notes, rows_dev) for (x, rows_dev, *_), (saved, _, notes) in zip(sides, states)]
+    ctx.params = [(weights, biases) for _, _, weights, biases, *_ in sides]      # the parameter OBJECTS (deferred weight gradients)
+    ys = tuple(y.view(*sd[0].shape[:-1], y.shape[-1]) for sd, (_, y, _) in zip(sides, states))
+    return ys if len(ys) > 1 else ys[0]
+
+
+def _node_backward(ctx, dys, recipe):
+    """`backward` of both nodes: the backward recipes of the sides whose gradient arrived, in step."""
+    need, saved, live, recipes, at = ctx.needs_input_grad, ctx.saved_tensors, [], [], 0
+    for dy, s, (n_saved, *meta), params in zip(dys, ctx.slots, ctx.meta, ctx.params):
+        if dy is not None:
+            live.append(s)
+            recipes.append(recipe(dy, saved[at:at + n_saved], *meta, *params, need[s.x], need[s.weights], need[s.biases]))
+        at += n_saved
+    out = [None] * ctx.slots[-1].extra.stop
+    for s, (dx, dws, dbs) in zip(live, _run(recipes)):
+        out[s.x], out[s.weights], out[s.biases] = dx, dws, dbs
+    return tuple(out)
 
 
 class _LinearFn(torch.autograd.Function):
-    """y = x W^T + b over the concatenation of n weight blocks (n = 1: a plain Linear)."""
+    """Per side y = x W^T + b over the concatenation of n weight blocks (n = 1: a plain Linear).  Two sides: the forward
+    products -- and, when both output gradients arrive together, the input-gradient products -- leave as one launch each."""
+    EXTRA, recipe = 0, staticmethod(_linear_forward)
 
     @staticmethod
-    def forward(ctx, x, n, *wb):
-        rows_dev = None
-        if len(wb) == 2 * n + 1:                             # optional trailing device-side row count
-            rows_dev, wb = wb[-1], wb[:-1]
-        weights, biases = wb[:n], wb[n:]
-        ahead = _PRECOMPUTED.pop(id(x), None)
-        if ahead is not None:
-            x16, w16, y = ahead
-        else:
-            w16, b32 = shadow_of(weights, biases)
-            x16 = _as_rows16(x)
-            y = linear_forward(x16, w16, b32, rows_dev=rows_dev)
-        ctx.rows_dev = rows_dev
-        ctx.save_for_backward(x16, w16)
-        ctx.meta = (x.shape, x.dtype, n, [w.shape[0] for w in weights], [b is not None for b in biases])
-        ctx.params = (weights, biases)                       # the parameter OBJECTS (deferred weight gradients)
-        return y.view(*x.shape[:-1], w16.shape[0])
+    def forward(ctx, *args):
+        return _node_forward(ctx, _LinearFn, *args)
 
     @staticmethod
-    def backward(ctx, dy):
-        x16, w16 = ctx.saved_tensors
-        x_shape, x_dtype, n, rows, has_b = ctx.meta
-        dy16 = _as_rows16(dy)
-        need_w = any(ctx.needs_input_grad[2:2 + n])
-        need_b = any(ctx.needs_input_grad[2 + n:])
-        dws, dbs = [None] * n, [None] * n
-        deferred = False
-        if need_w and all(ctx.needs_input_grad[2:2 + n]) and all((not hb) or g for hb, g in zip(has_b, ctx.needs_input_grad[2 + n:])):
-            deferred = _wgrad_to_params(dy16, x16, ctx.params[0], ctx.params[1], rows, ctx.rows_dev)      # side stream, first
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dx = linear_dgrad(dy16, w16, rows_dev=ctx.rows_dev).view(x_shape)
-            if dx.dtype != x_dtype:
-                dx = dx.to(x_dtype)
-        if (need_w or need_b) and not deferred:
-            dw, db = linear_wgrad(dy16, x16, want_bias=need_b, rows_dev=ctx.rows_dev)
-            r = 0
-            for i in range(n):
-                if ctx.needs_input_grad[2 + i]:
-                    dws[i] = dw[r:r + rows[i]]
-                if has_b[i] and ctx.needs_input_grad[2 + n + i]:
-                    dbs[i] = db[r:r + rows[i]]
-                r += rows[i]
-        return (dx, None, *dws, *dbs) + ((None,) if ctx.rows_dev is not None else ())
+    def backward(ctx, *dys):
+        return _node_backward(ctx, dys, _linear_backward)
 
 
-def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor],
-           rows_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
-    if rows_dev is not None:
-        return _LinearFn.apply(x, 1, weight, bias, rows_dev)
-    return _LinearFn.apply(x, 1, weight, bias)
+class _FFNFn(torch.autograd.Function):
+    """Per side y = dropout(act(x W1^T + b1)) W2^T + b2 : two forward GEMMs, four backward GEMMs, no elementwise launch.
+    Two sides: both first GEMMs as one launch, both second GEMMs as one launch; backward likewise when both gradients
+    arrive (else the side that did alone)."""
+    EXTRA, recipe = 3, staticmethod(_ffn_forward)            # act, p_drop, seed_dev
+
+    @staticmethod
+    def forward(ctx, *args):
+        return _node_forward(ctx, _FFNFn, *args)
+
+    @staticmethod
+    def backward(ctx, *dys):
+        return _node_backward(ctx, dys, _ffn_backward)
 
 
-def packed_linear(x: torch.Tensor, layers: Sequence[torch.nn.Linear], rows_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """One GEMM for several Linears that read the same input; output columns in the order given."""
-    extra = (rows_dev,) if rows_dev is not None else ()
-    return _LinearFn.apply(x, len(layers), *[m.weight for m in layers], *[m.bias for m in layers], *extra)
+_TWIN_BACKWARD = True    # False: paired forward products, SEPARATE autograd nodes (a backward pass that is cut between the
+#                          two stacks -- the split-graph data-parallel step runs them as two graphs -- must not meet a node
+#                          that belongs to both: it would run twice and drag the other stack's nodes along with undefined
+#                          gradients)
+
+
+def set_twin_backward(flag: bool) -> None:
+    global _TWIN_BACKWARD
+    _TWIN_BACKWARD = bool(flag)
+
+
+def _nodes(fn, sides) -> tuple:
+    """The outputs of `fn` over 1 or 2 sides: one node for all of them, or -- two sides, `_TWIN_BACKWARD` off -- the forward
+    recipes run in step here and one node per side that is handed its finished forward state and only saves it."""
+    def node(sides, ahead=None):
+        return fn.apply(tuple(len(sd[2]) for sd in sides), ahead, *_Slots.flat(sides))
+    if len(sides) == 1:
+        return (node(sides),)
+    if _TWIN_BACKWARD:
+        return node(sides)
+    with torch.no_grad():
+        ahead = _run([fn.recipe(*sd) for sd in sides])
+    return tuple(node([sd], [state]) for sd, state in zip(sides, ahead))
 
 
 class _LinearGeluFn(torch.autograd.Function):
@@ -877,81 +1048,12 @@ class _LinearGeluFn(torch.autograd.Function):
             dw, db = linear_wgrad(dpre, x16, want_bias=has_b, rows_dev=rd)
         dx = None
         if ctx.needs_input_grad[0]:
-            dx = linear_dgrad(dpre, w16, rows_dev=rd).view(x_shape)
-            if dx.dtype != x_dtype:
-                dx = dx.to(x_dtype)
+            dx = _dx_out(linear_dgrad(dpre, w16, rows_dev=rd), x_shape, x_dtype)
         return dx, dw, db, None
 
 
 def linear_gelu(x: torch.Tensor, linear: torch.nn.Linear, rows_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
     return _LinearGeluFn.apply(x, linear.weight, linear.bias, rows_dev)
-
-
-_GELU_FACTOR = True          # False: save the pre-activation and recompute gelu' and the mask in the backward epilogue (A/B, tests)
-
-
-def set_gelu_factor(flag: bool) -> None:
-    global _GELU_FACTOR
-    _GELU_FACTOR = bool(flag)
-
-
-class _FFNFn(torch.autograd.Function):
-    """y = dropout(act(x W1^T + b1)) W2^T + b2 : two forward GEMMs, four backward GEMMs, no elementwise launch."""
-
-    @staticmethod
-    def forward(ctx, x, w1, b1, w2, b2, act, p_drop, seed_dev, rows_dev=None):
-        ahead = _PRECOMPUTED.pop(id(x), None)
-        ctx.gelu_factor = act == "gelu" and _GELU_FACTOR
-        if ahead is not None:
-            x16, w1_16, w2_16, h, pre, y = ahead
-        else:
-            w1_16, b1_32 = shadow_of((w1,), (b1,))
-            w2_16, b2_32 = shadow_of((w2,), (b2,))
-            x16 = _as_rows16(x)
-            # gelu: the forward epilogue saves gelu'(pre) x dropout-mask / (1 - p) (one multiply per element in the backward
-            # epilogue instead of the erf terms and the mask hash: gps_gemm.hip EPI_BIAS_GELU_FACTOR / EPI_MUL_AUX)
-            h, pre = linear_forward(x16, w1_16, b1_32, act=act, p_drop=p_drop, seed_dev=seed_dev,
-                                    want_pre="factor" if ctx.gelu_factor else True, rows_dev=rows_dev)
-            y = linear_forward(h, w2_16, b2_32, rows_dev=rows_dev)
-        ctx.rows_dev = rows_dev
-        ctx.save_for_backward(x16, w1_16, w2_16, h, pre, seed_dev)
-        ctx.meta = (x.shape, x.dtype, act, float(p_drop), b1 is not None, b2 is not None)
-        ctx.params = (w1, b1, w2, b2)
-        return y.view(*x.shape[:-1], w2_16.shape[0])
-
-    @staticmethod
-    def backward(ctx, dy):
-        x16, w1_16, w2_16, h, pre, seed_dev = ctx.saved_tensors
-        x_shape, x_dtype, act, p_drop, has_b1, has_b2 = ctx.meta
-        dy16 = _as_rows16(dy)
-        w1, b1, w2, b2 = ctx.params
-        all_w = all(ctx.needs_input_grad[1:5][i] for i in (0, 2)) and (not has_b1 or ctx.needs_input_grad[2]) and \
-            (not has_b2 or ctx.needs_input_grad[4])
-        dw1 = db1 = dw2 = db2 = None
-        rd = ctx.rows_dev
-        if not (all_w and _wgrad_to_params(dy16, h, (w2,), (b2,), (w2.shape[0],), rd)):
-            dw2, db2 = linear_wgrad(dy16, h, want_bias=has_b2, rows_dev=rd)
-        dpre = linear_dgrad(dy16, w2_16, act="factor" if ctx.gelu_factor else act, aux=pre if act == "gelu" else h, p_drop=p_drop,
-                            seed_dev=seed_dev, rows_dev=rd)
-        if not (all_w and _wgrad_to_params(dpre, x16, (w1,), (b1,), (w1.shape[0],), rd)):
-            dw1, db1 = linear_wgrad(dpre, x16, want_bias=has_b1, rows_dev=rd)
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dx = linear_dgrad(dpre, w1_16, rows_dev=rd).view(x_shape)
-            if dx.dtype != x_dtype:
-                dx = dx.to(x_dtype)
-        return dx, dw1, db1, dw2, db2, None, None, None, None
-
-
-def ffn(x: torch.Tensor, linear1: torch.nn.Linear, linear2: torch.nn.Linear, act: str, p_drop: float,
-        training: bool, rows_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """act in {"gelu", "relu"}; dropout between activation and linear2 as the reference's layers apply it."""
-    p = float(p_drop) if training else 0.0
-    seed_dev = None
-    if p > 0.0:
-        from .fused_attention import _next_device_seed
-        seed_dev = _next_device_seed(x.device)
-    return _FFNFn.apply(x, linear1.weight, linear1.bias, linear2.weight, linear2.bias, act, p, seed_dev, rows_dev)
 
 
 # ---- two independent stacks in lock-step: paired products --------------------------------------------------------------------
@@ -960,13 +1062,15 @@ def ffn(x: torch.Tensor, linear1: torch.nn.Linear, linear2: torch.nn.Linear, act
 # projection -> residual LayerNorm -> FFN -> residual LayerNorm.  Launched one stack after the other their 768-wide GEMMs
 # are 150 (text, 12 608 live rows) and 60 (objects) tiles of 256 x 256 on 256 CUs.  Here the layer code of either stack is a
 # GENERATOR that yields its GEMM calls (`LinearOp`, `FFNOp`) instead of making them; `drive(gen)` executes them one by one
-# (the ordinary forward), `drive_pair(gen_a, gen_b)` advances both stacks in step and issues the two products of a pair as
-# one launch (`_TwinLinearFn`, `_TwinFFNFn`: ONE autograd node per pair, so that the backward pass pairs the input-gradient
-# GEMMs the same way; weight gradients already leave grouped -- `grouped_wgrads`).  tools/probes/gemm_probe group: the
-# eight forward / input-gradient launches of one layer pair 849 -> 616 us.
+# (the ordinary forward: a one-side `_LinearFn` / `_FFNFn`), `drive_pair(gen_a, gen_b)` advances both stacks in step and hands
+# the two ops of a pair to ONE two-side node, whose recipes leave stage by stage as one launch per stage -- forward, and
+# backward too: the input-gradient GEMMs pair the same way (weight gradients already leave grouped -- `grouped_wgrads`).
+# With `set_twin_backward(False)` only the forward products pair and every side keeps a node of its own (`_nodes`).
+# tools/probes/gemm_probe group: the eight forward / input-gradient launches of one layer pair 849 -> 616 us.
 class LinearOp:
     """y = x [W_0; W_1; ...]^T + [b_0; ...] (`packed_linear`; one Linear: `linear`)."""
     __slots__ = ("x", "weights", "biases", "rows_dev")
+    fn = _LinearFn
 
     def __init__(self, x, weights, biases, rows_dev=None):
         self.x, self.weights, self.biases, self.rows_dev = x, tuple(weights), tuple(biases), rows_dev
@@ -975,21 +1079,49 @@ class LinearOp:
     def of(x, layers: Sequence[torch.nn.Linear], rows_dev=None) -> "LinearOp":
         return LinearOp(x, [m.weight for m in layers], [m.bias for m in layers], rows_dev)
 
+    def side(self) -> tuple:
+        return self.x, self.rows_dev, self.weights, self.biases
+
     def run(self):
-        extra = (self.rows_dev,) if self.rows_dev is not None else ()
-        return _LinearFn.apply(self.x, len(self.weights), *self.weights, *self.biases, *extra)
+        return _nodes(self.fn, [self.side()])[0]
 
 
 class FFNOp:
     """y = dropout(act(x W1^T + b1)) W2^T + b2 (`ffn`)."""
     __slots__ = ("x", "linear1", "linear2", "act", "p_drop", "training", "rows_dev")
+    fn = _FFNFn
 
     def __init__(self, x, linear1, linear2, act, p_drop, training, rows_dev=None):
         self.x, self.linear1, self.linear2, self.act = x, linear1, linear2, act
         self.p_drop, self.training, self.rows_dev = float(p_drop), bool(training), rows_dev
 
-    def run(self):
-        return ffn(self.x, self.linear1, self.linear2, self.act, self.p_drop, self.training, rows_dev=self.rows_dev)
+    def side(self) -> tuple:
+        """Draws the dropout seed: called at the moment the op (side a of a pair before side b) is executed."""
+        p = self.p_drop if self.training else 0.0
+        seed_dev = None
+        if p > 0.0:
+            from .fused_attention import _next_device_seed
+            seed_dev = _next_device_seed(self.x.device)
+        l1, l2 = self.linear1, self.linear2
+        return self.x, self.rows_dev, (l1.weight, l2.weight), (l1.bias, l2.bias), self.act, p, seed_dev
+
+    run = LinearOp.run
+
+
+def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor],
+           rows_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
+    return LinearOp(x, (weight,), (bias,), rows_dev).run()
+
+
+def packed_linear(x: torch.Tensor, layers: Sequence[torch.nn.Linear], rows_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One GEMM for several Linears that read the same input; output columns in the order given."""
+    return LinearOp.of(x, layers, rows_dev).run()
+
+
+def ffn(x: torch.Tensor, linear1: torch.nn.Linear, linear2: torch.nn.Linear, act: str, p_drop: float,
+        training: bool, rows_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """act in {"gelu", "relu"}; dropout between activation and linear2 as the reference's layers apply it."""
+    return FFNOp(x, linear1, linear2, act, p_drop, training, rows_dev).run()
 
 
 def _step(gen, value, first):
@@ -1032,12 +1164,8 @@ def drive_pair(gen_a, gen_b):
             op_b, done_b = _step(gen_b, op_b.run(), False)
         elif done_b is not None:
             op_a, done_a = _step(gen_a, op_a.run(), False)
-        elif isinstance(op_a, LinearOp) and isinstance(op_b, LinearOp):
-            ya, yb = _twin_linear(op_a, op_b)
-            op_a, done_a = _step(gen_a, ya, False)
-            op_b, done_b = _step(gen_b, yb, False)
-        elif isinstance(op_a, FFNOp) and isinstance(op_b, FFNOp) and op_a.act == op_b.act:
-            ya, yb = _twin_ffn(op_a, op_b)
+        elif type(op_a) is type(op_b) and (isinstance(op_a, LinearOp) or op_a.act == op_b.act):
+            ya, yb = _nodes(op_a.fn, [op_a.side(), op_b.side()])
             op_a, done_a = _step(gen_a, ya, False)
             op_b, done_b = _step(gen_b, yb, False)
         else:
@@ -1047,226 +1175,6 @@ def drive_pair(gen_a, gen_b):
             else:
                 op_b, done_b = _step(gen_b, op_b.run(), False)
     return done_a[0], done_b[0]
-
-
-def _dx_out(dx, shape, dtype):
-    dx = dx.view(shape)
-    return dx if dx.dtype == dtype else dx.to(dtype)
-
-
-class _TwinLinearFn(torch.autograd.Function):
-    """(y_a, y_b) = (`_LinearFn` of side a, `_LinearFn` of side b) with the two forward products -- and, when both output
-    gradients arrive together, the two input-gradient products -- issued as one launch each.  A backward call that brings
-    only one side's gradient (the split-graph data-parallel step runs the text and the object encoder's backward as two
-    graphs) computes that side alone."""
-
-    @staticmethod
-    def forward(ctx, xa, xb, na, nb, rows_a, rows_b, *wb):
-        ctx.set_materialize_grads(False)
-        sides, at = [], 0
-        for x, n, rows_dev in ((xa, na, rows_a), (xb, nb, rows_b)):
-            weights, biases = wb[at:at + n], wb[at + n:at + 2 * n]
-            at += 2 * n
-            w16, b32 = shadow_of(weights, biases)
-            x16 = _as_rows16(x)
-            q, y, _ = _forward_product(x16, w16, b32, rows_dev=rows_dev)
-            sides.append((q, y, x16, w16, x.shape, x.dtype, weights, biases, rows_dev))
-        _launch_together([sd[0] for sd in sides])
-        ctx.save_for_backward(sides[0][2], sides[0][3], sides[1][2], sides[1][3])
-        ctx.meta = [(sd[4], sd[5], [w.shape[0] for w in sd[6]], [b is not None for b in sd[7]]) for sd in sides]
-        ctx.params = [(sd[6], sd[7]) for sd in sides]
-        ctx.rows_dev = [sd[8] for sd in sides]
-        ctx.n = (na, nb)
-        return tuple(sd[1].view(*sd[4][:-1], sd[3].shape[0]) for sd in sides)
-
-    @staticmethod
-    def backward(ctx, dya, dyb):
-        saved = ctx.saved_tensors
-        na, nb = ctx.n
-        need = ctx.needs_input_grad
-        grads_x, grads_wb, products, finish = [None, None], [], [], []
-        at = 6
-        for side, (dy, n) in enumerate(((dya, na), (dyb, nb))):
-            x16, w16 = saved[2 * side], saved[2 * side + 1]
-            x_shape, x_dtype, rows, has_b = ctx.meta[side]
-            need_ws, need_bs = need[at:at + n], need[at + n:at + 2 * n]
-            at += 2 * n
-            dws, dbs = [None] * n, [None] * n
-            if dy is not None:
-                dy16 = _as_rows16(dy)
-                rd = ctx.rows_dev[side]
-                deferred = False
-                if any(need_ws) and all(need_ws) and all((not hb) or g for hb, g in zip(has_b, need_bs)):
-                    deferred = _wgrad_to_params(dy16, x16, ctx.params[side][0], ctx.params[side][1], rows, rd)
-                if need[side]:
-                    q, dx = _dgrad_product(dy16, w16, rows_dev=rd)
-                    products.append(q)
-                    finish.append((side, dx, x_shape, x_dtype))
-                if (any(need_ws) or any(need_bs)) and not deferred:
-                    dw, db = linear_wgrad(dy16, x16, want_bias=any(need_bs), rows_dev=rd)
-                    r = 0
-                    for i in range(n):
-                        if need_ws[i]:
-                            dws[i] = dw[r:r + rows[i]]
-                        if has_b[i] and need_bs[i]:
-                            dbs[i] = db[r:r + rows[i]]
-                        r += rows[i]
-            grads_wb += dws + dbs
-        _launch_together(products)
-        for side, dx, x_shape, x_dtype in finish:
-            grads_x[side] = _dx_out(dx, x_shape, x_dtype)
-        return (grads_x[0], grads_x[1], None, None, None, None, *grads_wb)
-
-
-_TWIN_BACKWARD = True    # False: paired forward products, SEPARATE autograd nodes (a backward pass that is cut between the
-#                          two stacks -- the split-graph data-parallel step runs them as two graphs -- must not meet a node
-#                          that belongs to both: it would run twice and drag the other stack's nodes along with undefined
-#                          gradients)
-
-
-def set_twin_backward(flag: bool) -> None:
-    global _TWIN_BACKWARD
-    _TWIN_BACKWARD = bool(flag)
-
-
-def _twin_linear_forward_only(op_a: LinearOp, op_b: LinearOp):
-    ahead = []
-    with torch.no_grad():
-        for op in (op_a, op_b):
-            w16, b32 = shadow_of(op.weights, op.biases)
-            x16 = _as_rows16(op.x)
-            q, y, _ = _forward_product(x16, w16, b32, rows_dev=op.rows_dev)
-            ahead.append((q, (x16, w16, y)))
-        _launch_together([q for q, _ in ahead])
-    outs = []
-    for op, (_, res) in zip((op_a, op_b), ahead):
-        _PRECOMPUTED[id(op.x)] = res
-        try:
-            outs.append(op.run())
-        finally:
-            _PRECOMPUTED.pop(id(op.x), None)
-    return tuple(outs)
-
-
-def _twin_ffn_forward_only(op_a: FFNOp, op_b: FFNOp):
-    from .fused_attention import _next_device_seed
-    factor = op_a.act == "gelu" and _GELU_FACTOR
-    st = []
-    with torch.no_grad():
-        for op in (op_a, op_b):
-            p = op.p_drop if op.training else 0.0
-            seed = _next_device_seed(op.x.device) if p > 0.0 else None
-            w1_16, b1_32 = shadow_of((op.linear1.weight,), (op.linear1.bias,))
-            w2_16, b2_32 = shadow_of((op.linear2.weight,), (op.linear2.bias,))
-            x16 = _as_rows16(op.x)
-            q1, h, pre = _forward_product(x16, w1_16, b1_32, act=op.act, p_drop=p, seed_dev=seed,
-                                          want_pre="factor" if factor else True, rows_dev=op.rows_dev)
-            st.append(dict(op=op, p=p, seed=seed, x16=x16, w1_16=w1_16, w2_16=w2_16, b2_32=b2_32, q1=q1, h=h, pre=pre))
-        _launch_together([d["q1"] for d in st])
-        for d in st:
-            d["q2"], d["y"], _ = _forward_product(d["h"], d["w2_16"], d["b2_32"], rows_dev=d["op"].rows_dev)
-        _launch_together([d["q2"] for d in st])
-    outs = []
-    for d in st:
-        op = d["op"]
-        _PRECOMPUTED[id(op.x)] = (d["x16"], d["w1_16"], d["w2_16"], d["h"], d["pre"], d["y"])
-        try:
-            outs.append(_FFNFn.apply(op.x, op.linear1.weight, op.linear1.bias, op.linear2.weight, op.linear2.bias, op.act,
-                                     d["p"], d["seed"], op.rows_dev))
-        finally:
-            _PRECOMPUTED.pop(id(op.x), None)
-    return tuple(outs)
-
-
-def _twin_linear(op_a: LinearOp, op_b: LinearOp):
-    if not _TWIN_BACKWARD:
-        return _twin_linear_forward_only(op_a, op_b)
-    return _TwinLinearFn.apply(op_a.x, op_b.x, len(op_a.weights), len(op_b.weights), op_a.rows_dev, op_b.rows_dev,
-                               *op_a.weights, *op_a.biases, *op_b.weights, *op_b.biases)
-
-
-class _TwinFFNFn(torch.autograd.Function):
-    """(y_a, y_b) = (`_FFNFn` of side a, `_FFNFn` of side b): both first GEMMs as one launch, both second GEMMs as one
-    launch; backward likewise when both gradients arrive (else the side that did alone)."""
-
-    @staticmethod
-    def forward(ctx, xa, xb, act, pa, pb, seed_a, seed_b, rows_a, rows_b, w1a, b1a, w2a, b2a, w1b, b1b, w2b, b2b):
-        ctx.set_materialize_grads(False)
-        factor = act == "gelu" and _GELU_FACTOR
-        st = []
-        for x, p, seed, rd, w1, b1, w2, b2 in ((xa, pa, seed_a, rows_a, w1a, b1a, w2a, b2a), (xb, pb, seed_b, rows_b, w1b, b1b, w2b, b2b)):
-            w1_16, b1_32 = shadow_of((w1,), (b1,))
-            w2_16, b2_32 = shadow_of((w2,), (b2,))
-            x16 = _as_rows16(x)
-            q1, h, pre = _forward_product(x16, w1_16, b1_32, act=act, p_drop=p, seed_dev=seed,
-                                          want_pre="factor" if factor else True, rows_dev=rd)
-            st.append(dict(x=x, x16=x16, w1_16=w1_16, w2_16=w2_16, b2_32=b2_32, q1=q1, h=h, pre=pre, p=p, seed=seed, rd=rd,
-                           params=(w1, b1, w2, b2)))
-        _launch_together([d["q1"] for d in st])
-        ys = []
-        for d in st:
-            d["q2"], y, _ = _forward_product(d["h"], d["w2_16"], d["b2_32"], rows_dev=d["rd"])
-            ys.append(y)
-        _launch_together([d["q2"] for d in st])
-        ctx.save_for_backward(*[t for d in st for t in (d["x16"], d["w1_16"], d["w2_16"], d["h"], d["pre"], d["seed"])])
-        ctx.meta = [(d["x"].shape, d["x"].dtype, float(d["p"]), d["params"][1] is not None, d["params"][3] is not None) for d in st]
-        ctx.params = [d["params"] for d in st]
-        ctx.rows_dev = [d["rd"] for d in st]
-        ctx.act, ctx.gelu_factor = act, factor
-        return tuple(y.view(*d["x"].shape[:-1], d["w2_16"].shape[0]) for y, d in zip(ys, st))
-
-    @staticmethod
-    def backward(ctx, dya, dyb):
-        saved, need, act = ctx.saved_tensors, ctx.needs_input_grad, ctx.act
-        live = []
-        grads = {}
-        for side, dy in enumerate((dya, dyb)):
-            if dy is None:
-                continue
-            x16, w1_16, w2_16, h, pre, seed = saved[6 * side:6 * side + 6]
-            x_shape, x_dtype, p, has_b1, has_b2 = ctx.meta[side]
-            w1, b1, w2, b2 = ctx.params[side]
-            nw = need[9 + 4 * side:13 + 4 * side]
-            all_w = nw[0] and nw[2] and (not has_b1 or nw[1]) and (not has_b2 or nw[3])
-            live.append(dict(side=side, dy16=_as_rows16(dy), x16=x16, w1_16=w1_16, w2_16=w2_16, h=h, pre=pre, seed=seed,
-                             x_shape=x_shape, x_dtype=x_dtype, p=p, has_b1=has_b1, has_b2=has_b2, w1=w1, b1=b1, w2=w2, b2=b2,
-                             all_w=all_w, rd=ctx.rows_dev[side], dw1=None, db1=None, dw2=None, db2=None))
-        for d in live:
-            if not (d["all_w"] and _wgrad_to_params(d["dy16"], d["h"], (d["w2"],), (d["b2"],), (d["w2"].shape[0],), d["rd"])):
-                d["dw2"], d["db2"] = linear_wgrad(d["dy16"], d["h"], want_bias=d["has_b2"], rows_dev=d["rd"])
-            d["q"], d["dpre"] = _dgrad_product(d["dy16"], d["w2_16"], act="factor" if ctx.gelu_factor else act,
-                                               aux=d["pre"] if act == "gelu" else d["h"], p_drop=d["p"], seed_dev=d["seed"],
-                                               rows_dev=d["rd"])
-        _launch_together([d["q"] for d in live])
-        products = []
-        for d in live:
-            if not (d["all_w"] and _wgrad_to_params(d["dpre"], d["x16"], (d["w1"],), (d["b1"],), (d["w1"].shape[0],), d["rd"])):
-                d["dw1"], d["db1"] = linear_wgrad(d["dpre"], d["x16"], want_bias=d["has_b1"], rows_dev=d["rd"])
-            d["dx"] = None
-            if need[d["side"]]:
-                q, d["dx"] = _dgrad_product(d["dpre"], d["w1_16"], rows_dev=d["rd"])
-                products.append(q)
-        _launch_together(products)
-        out = [None] * 17
-        for d in live:
-            if d["dx"] is not None:
-                out[d["side"]] = _dx_out(d["dx"], d["x_shape"], d["x_dtype"])
-            out[9 + 4 * d["side"]:13 + 4 * d["side"]] = [d["dw1"], d["db1"], d["dw2"], d["db2"]]
-        return tuple(out)
-
-
-def _twin_ffn(op_a: FFNOp, op_b: FFNOp):
-    from .fused_attention import _next_device_seed
-    if not _TWIN_BACKWARD:
-        return _twin_ffn_forward_only(op_a, op_b)
-    ps, seeds = [], []
-    for op in (op_a, op_b):
-        p = op.p_drop if op.training else 0.0
-        ps.append(p)
-        seeds.append(_next_device_seed(op.x.device) if p > 0.0 else None)
-    return _TwinFFNFn.apply(op_a.x, op_b.x, op_a.act, ps[0], ps[1], seeds[0], seeds[1], op_a.rows_dev, op_b.rows_dev,
-                            op_a.linear1.weight, op_a.linear1.bias, op_a.linear2.weight, op_a.linear2.bias,
-                            op_b.linear1.weight, op_b.linear1.bias, op_b.linear2.weight, op_b.linear2.bias)
 
 
 def activation_name(fn) -> Optional[str]:

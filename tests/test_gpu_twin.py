@@ -149,6 +149,59 @@ def test_lock_step_backward_with_one_side_only(twin_backward):
     assert xb.grad is not None
 
 
+def _bits(t):
+    return t.contiguous().view(torch.int16 if t.element_size() == 2 else torch.int32)
+
+
+def _paired_and_sequential_one_by_one(monkeypatch, act, twin_backward, rows_a=None):
+    """`_launch_together` reduced to launching its products one by one: the lock-step paths then issue exactly the
+    launches of the sequential paths.  -> per mode [ya, yb, xa.grad, xb.grad, every parameter gradient]."""
+    from sceneverse_amd.modules.layers import gemm
+    monkeypatch.setattr(gemm, "_launch_together", lambda products: [gemm._launch(q) for q in products if q is not None])
+    gemm.set_twin_backward(twin_backward)
+    sa, sb = _stack(256, 512, 1, 5), _stack(256, 512, 2, 6)
+    params = list(sa.parameters()) + list(sb.parameters())
+    xa0 = torch.randn(300, 256, device=DEV).to(torch.bfloat16)       # 300 rows: the last tile is ragged
+    xb0 = torch.randn(3, 100, 256, device=DEV).to(torch.bfloat16)
+    rows_dev = torch.tensor([rows_a], dtype=torch.int32, device=DEV) if rows_a is not None else None
+    live = rows_a if rows_a is not None else xa0.shape[0]
+    res = {}
+    try:
+        for mode in ("sequential", "paired"):
+            for p in params:
+                p.grad = None
+            xa, xb = xa0.clone().requires_grad_(True), xb0.clone().requires_grad_(True)
+            if mode == "paired":
+                ya, yb = gemm.drive_pair(_stack_gen(sa, xa, act, rows_dev), _stack_gen(sb, xb, act))
+            else:
+                ya, yb = gemm.drive(_stack_gen(sa, xa, act, rows_dev)), gemm.drive(_stack_gen(sb, xb, act))
+            (ya[:live].float().square().mean() + yb.float().square().mean()).backward()
+            res[mode] = [ya.detach()[:live], yb.detach(), xa.grad[:live], xb.grad] + [p.grad.clone() for p in params]
+    finally:
+        gemm.set_twin_backward(True)
+    return res
+
+
+@pytest.mark.parametrize("twin_backward", [True, False], ids=["paired-backward", "forward-only"])
+@pytest.mark.parametrize("act", ["gelu", "relu"])
+def test_lock_step_launches_one_by_one_are_bit_equal_to_sequential(monkeypatch, act, twin_backward):
+    res = _paired_and_sequential_one_by_one(monkeypatch, act, twin_backward)
+    for i, (s, p) in enumerate(zip(res["sequential"], res["paired"])):
+        assert s.shape == p.shape and s.dtype == p.dtype and torch.equal(_bits(s), _bits(p)), f"tensor {i}"
+        assert torch.isfinite(p.float()).all(), f"tensor {i}"
+
+
+@pytest.mark.parametrize("twin_backward", [True, False], ids=["paired-backward", "forward-only"])
+@pytest.mark.parametrize("act", ["gelu", "relu"])
+def test_lock_step_launches_one_by_one_with_row_extent_are_bit_equal(monkeypatch, act, twin_backward):
+    """Side a carries work on 250 of its 300 rows (device-side extent): rows past it are unwritten by design, so its
+    output and input gradient are compared on the live rows; every parameter gradient whole."""
+    res = _paired_and_sequential_one_by_one(monkeypatch, act, twin_backward, rows_a=250)
+    for i, (s, p) in enumerate(zip(res["sequential"], res["paired"])):
+        assert s.shape == p.shape and s.dtype == p.dtype and torch.equal(_bits(s), _bits(p)), f"tensor {i}"
+        assert torch.isfinite(p.float()).all(), f"tensor {i}"
+
+
 def test_gps_model_paired_stacks_equal_unpaired(golden_cpu):
     from oracle.param_fill import fill_params
     from sceneverse_amd.model.build import build_model
