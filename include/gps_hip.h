@@ -80,7 +80,7 @@ GPS_API int gps_furthest_point_sampling_xyz(int b, int n, int m, const float *da
  * gps_point_set_object_extent(p): while p is not NULL the per-object launches of gps_furthest_point_sampling[_xyz]
  * (register-resident form), gps_ball_query, gps_sa_mlp_forward*, gps_split3_points process objects [0, *p) only and
  * neither read nor write the others (p = scal of the plan; device memory; a setting of the CALLING HOST THREAD -- launches
- * issued by other threads never see it; gps_sa_mlp_set_products is process-wide -- set it around the encoder's launches,
+ * issued by other threads never see it; gps_sa_mlp_set_products / gps_sa_mlp_set_distinct are process-wide -- set it around the encoder's launches,
  * reset it to NULL afterwards).  Per-object results do not depend on the other
  * objects of the batch, so result[slot_of[o]] is bit-identical to running every object. */
 GPS_API int gps_cloud_compact(int b, int n, int ld, const float *cloud, int rows_mult, int32_t *flag_scratch,
@@ -199,6 +199,16 @@ GPS_API long long gps_sa_mlp_layer_floats_bf16x3(int c_in, int c_out);
  * third of the MFMA work, features within 2e-2 of the fp32 path's scale (tests/test_gpu_sa_fused.py states the
  * measured figure).  Opt-in, process-wide; anything else = query.  Returns the previous setting. */
 GPS_API int gps_sa_mlp_set_products(int n);
+/* gps_sa_mlp_forward_bf16x3[_pm] on each group's DISTINCT samples only.  gps_ball_query fills the slots past the points it
+ * found with the group's first hit; slot c > 0 with idx[c] == idx[0] repeats the MLP column of slot 0, which the max-pool
+ * cannot see.  The rule is applied to whatever idx holds, so every setting pools the same values for any idx (equal as
+ * values; a pooled zero is always +0 in the distinct form).
+ *   0  every launch runs the MLP on all 32 slots (the dense kernels);
+ *   1  (default) the streamed-weight form (128 -> 128-128-256, SA2) runs on the distinct samples, several objects per
+ *      workgroup; the resident-weight form (3 -> 64-64-128, SA1) stays dense: there the distinct form measured slower;
+ *   2  both forms run on the distinct samples.
+ * Process-wide; anything else = query.  Returns the previous setting. */
+GPS_API int gps_sa_mlp_set_distinct(int on);
 GPS_API int gps_sa_mlp_pack_layer_bf16x3(int c_in, int c_out, const float *w, const float *shift, float *dst,
                                          gps_stream_t stream);
 GPS_API int gps_sa_mlp_forward_bf16x3(int b, int n, int npoint, int nsample, int c_feat, int c1, int c2,

@@ -13,7 +13,8 @@
 //   * one 256-thread workgroup per object; the object's points/features/indices are staged once in
 //     LDS (coalesced 16-byte loads), so the grouped (3+C, npoint, nsample) tensor -- 268 KB per
 //     object at SA2, the largest HBM stream of the point path -- never exists in HBM;
-//   * a wave owns one group = one 32-column tile (nsample == 32) through ALL three layers.  Layers
+//   * a wave owns one group = one 32-column tile (nsample == 32) through ALL three layers (dense kernels; the distinct-sample
+//     form of the split-bf16 variant, below, owns 32 columns of a compacted list instead -- default at SA2).  Layers
 //     run on v_mfma_f32_32x32x2_f32 (fp32 in, fp32 accumulate: bitwise an fmaf chain, so results
 //     stay within fp32 summation-order noise of the reference's fp32 conv).  The D fragment of one
 //     layer (lane = column, registers = rows) IS the B fragment of the next layer's MFMAs once the
@@ -23,6 +24,11 @@
 //     tile); folded BN shift initialises the accumulator, ReLU is one v_max per register;
 //   * max over the 32 samples = DPP row reduction + row_bcast15; pooled rows are collected in LDS
 //     and written with coalesced stores.
+//
+//   * split-bf16 form (namespace x3, the default precision): the streamed-weight level (SA2) runs the MLP on each
+//     group's DISTINCT samples only -- the ball query's filler slots repeat slot 0 and cannot change the max -- with a
+//     compact column list in LDS, several objects per workgroup and a segmented max-pool (sa_mlp_x3_distinct_kernel;
+//     gps_sa_mlp_set_distinct).  The dense kernels below stay as the reference and as the resident-weight level (SA1).
 //
 // K-slot order.  For v_mfma_f32_32x32x2_f32 lane l holds A[i = l&31][k = l>>5], B[k = l>>5][j = l&31]
 // and D[row = (r&3) + 8*(r>>2) + 4*(l>>5)][col = l&31] in register r.  Input channels are therefore
@@ -629,15 +635,368 @@ __global__ __launch_bounds__(WAVES * 64) void sa_mlp_x3_kernel(
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// Distinct-sample form (default; gps_sa_mlp_set_distinct).  gps_ball_query fills the slots of a group past the points
+// it found with the group's first hit, so slot c > 0 with idx[c] == idx[0] is the same point, the same centre and the
+// same MLP column as slot 0: the max-pool cannot see it.  The rule is applied to whatever idx holds (it does not assume
+// that the kept slots form a prefix), so the pooled features are those of the dense kernel above for any idx.
+//   * after staging, the workgroup builds in LDS the list of kept (group, point) columns, group after group (ballot +
+//     prefix count per group, one prefix sum over the groups); one tile = 32 consecutive list entries, the layer-1
+//     operands are gathered per lane from the entry's own point and its own group's centre; tiles past the end of the
+//     list are not computed, lanes past the end of the last tile repeat the last entry and are not pooled;
+//   * a group's columns may straddle tiles and waves: each lane keeps a running max over its registers' runs of equal
+//     group and folds a run into the group's pooled row with an LDS integer max on the bit pattern (rows start at +0,
+//     which is also the ReLU after the max; max is order-independent, so the result is deterministic; on the bit pattern
+//     a positive NaN is the largest value and is kept, where the dense form's fmaxf drops it).  The pooled
+//     rows are kept [group][channel] with a pitch of C3 + 1 words: conflict-free for the lanes (= channels) of a fold
+//     and for the transposing copy-out;
+//   * OBJS > 1 (streamed weights, SA2): a workgroup takes OBJS consecutive objects and ONE list over them, so that a
+//     streamed weight tile feeds up to WAVES tiles of columns although one object has about three; objects past the
+//     device-side extent are neither read nor written.
+// ------------------------------------------------------------------------------------------
+#ifndef GPS_SA2_OBJS
+#define GPS_SA2_OBJS 3   // objects per workgroup of the streamed form (LDS admits 1..3 at n = 32, npoint = 16)
+#endif
+
+template <int CF, int C1, int C2, int C3, int WAVES, bool RESIDENT, bool PM, int NPROD, int OBJS>
+__global__ __launch_bounds__(WAVES * 64) void sa_mlp_x3_distinct_kernel(
+    int b, int n, int npoint, const float *__restrict__ xyz, const float *__restrict__ new_xyz,
+    const float *__restrict__ feats, const int32_t *__restrict__ idx,
+    const float *__restrict__ wpack, float *__restrict__ out, int ld_feat, const int *__restrict__ n_obj_dev) {
+  int n_obj = b;
+  if (n_obj_dev) { const int ext = *n_obj_dev; n_obj = ext < b ? ext : b; }
+  const int obj0 = blockIdx.x * OBJS;
+  if (obj0 >= n_obj) return;                                   // object extent: nothing read or written
+  const int nobj = n_obj - obj0 < OBJS ? n_obj - obj0 : OBJS;  // objects of this workgroup
+  constexpr int BLOCK = WAVES * 64;
+  constexpr int CIN = 3 + CF;
+  constexpr int S1 = steps16(CIN), S2 = C1 / 16, S3 = C2 / 16;
+  constexpr int T1 = tile_floats16(CIN), T2 = tile_floats16(C1), T3 = tile_floats16(C2);
+  constexpr int M1 = C1 / 32, M2 = C2 / 32, M3 = C3 / 32;
+  constexpr int TMAX = T1 > T2 ? (T1 > T3 ? T1 : T3) : (T2 > T3 ? T2 : T3);
+  constexpr int TOTAL = M1 * T1 + M2 * T2 + M3 * T3;
+  constexpr int G = M1 + M2 + M3;
+  constexpr int WBUF = RESIDENT ? TOTAL : 2 * TMAX;
+  constexpr int OLD = C3 + 1;                // pitch of a pooled row
+
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  float *s_w0 = lds;
+  float *s_w1 = s_w0 + TMAX;                 // streaming form only
+  int *s_out = reinterpret_cast<int *>(lds + WBUF);             // [OBJS * npoint][OLD] bit patterns
+  float *s_feat = lds + WBUF + ((OBJS * npoint * OLD + 3) & ~3);  // [OBJS][CF][n]
+  float *s_xyz = s_feat + OBJS * CF * n;     // [OBJS][n][3]
+  float *s_ctr = s_xyz + OBJS * n * 3;       // [OBJS * npoint][3]
+  int32_t *s_idx = reinterpret_cast<int32_t *>(s_ctr + OBJS * npoint * 3);   // [OBJS * npoint][32]
+  int32_t *s_list = s_idx + OBJS * npoint * kNS;                // kept columns: group << 16 | point
+  int32_t *s_off = s_list + OBJS * npoint * kNS;                // [OBJS * npoint + 1] first list entry of a group
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int col = lane & 31, h = lane >> 5;
+  const int NG = nobj * npoint;              // groups of this workgroup
+
+  tile_copy_async<WAVES>(wpack, s_w0, RESIDENT ? TOTAL : T1, wave, lane);
+  {
+    const float *gx = xyz + (size_t)obj0 * n * 3;
+    const float *gc = new_xyz + (size_t)obj0 * npoint * 3;
+    const int32_t *gi = idx + (size_t)obj0 * npoint * kNS;
+    if (PM) {
+      const float *gf = feats + (size_t)obj0 * n * ld_feat;
+      for (int e = tid; e < nobj * CF * n; e += BLOCK) {
+        const int pp = e / CF, c = e - pp * CF;                 // pp = o * n + p
+        const int o = OBJS > 1 ? pp / n : 0;
+        s_feat[o * CF * n + c * n + (pp - o * n)] = gf[(size_t)pp * ld_feat + c];
+      }
+    } else {
+      const float *gf = feats + (size_t)obj0 * CF * n;
+      if (((CF * n) & 3) == 0) {
+        const float4 *g4 = reinterpret_cast<const float4 *>(gf);
+        float4 *l4 = reinterpret_cast<float4 *>(s_feat);
+        for (int e = tid; e < (nobj * CF * n) >> 2; e += BLOCK) l4[e] = g4[e];
+      } else {
+        for (int e = tid; e < nobj * CF * n; e += BLOCK) s_feat[e] = gf[e];
+      }
+    }
+    for (int e = tid; e < nobj * n * 3; e += BLOCK) s_xyz[e] = gx[e];
+    for (int e = tid; e < NG * 3; e += BLOCK) s_ctr[e] = gc[e];
+    for (int e = tid; e < NG * kNS; e += BLOCK) s_idx[e] = gi[e];
+    for (int e = tid; e < NG * OLD; e += BLOCK) s_out[e] = 0;
+  }
+  __syncthreads();
+
+  // ---- the kept columns: slot c > 0 of a group is dropped iff idx[c] == idx[0] -----------------------------------
+  // a half wave per group; pass 0 counts, pass 1 writes the list at the group's offset
+  auto scan_groups = [&](bool write) {
+    for (int g0 = wave * 2; g0 < NG; g0 += WAVES * 2) {
+      const int g = g0 + h;
+      const bool valid = g < NG;
+      const int p = valid ? s_idx[g * kNS + col] : 0;
+      const int p0 = __shfl(p, h * 32, 64);
+      const bool keep = valid && (col == 0 || p != p0);
+      const unsigned int hm = (unsigned int)(__ballot(keep) >> (32 * h));
+      if (!write) {
+        if (col == 0 && valid) s_off[g] = __popc(hm);
+      } else if (keep) {
+        s_list[s_off[g] + __popc(hm & ((1u << col) - 1u))] = (g << 16) | (p & 0xFFFF);
+      }
+    }
+  };
+  scan_groups(false);
+  __syncthreads();
+  if (wave == 0) {                           // exclusive prefix sum of the counts, total in s_off[NG]
+    int run = 0;
+    for (int base = 0; base < NG; base += 64) {
+      const bool in = base + lane < NG;
+      const int c = in ? s_off[base + lane] : 0;
+      int inc = c;
+#pragma unroll
+      for (int d = 1; d < 64; d <<= 1) {
+        const int t = __shfl_up(inc, d, 64);
+        if (lane >= d) inc += t;
+      }
+      if (in) s_off[base + lane] = run + inc - c;
+      run += __shfl(inc, 63, 64);
+    }
+    if (lane == 0) s_off[NG] = run;
+  }
+  __syncthreads();
+  scan_groups(true);
+  tile_copy_wait();
+  __syncthreads();
+
+  auto tile_off = [&](int g, int &len) -> int {      // offset (floats) of weight tile g (mod G)
+    if (g >= G) g -= G;
+    if (g < M1) { len = T1; return g * T1; }
+    if (g < M1 + M2) { len = T2; return M1 * T1 + (g - M1) * T2; }
+    len = T3;
+    return M1 * T1 + M2 * T2 + (g - M1 - M2) * T3;
+  };
+  auto stage_begin = [&](int rd, int g) -> const float * {
+    int len;
+    if (RESIDENT) return s_w0 + tile_off(g, len);
+    const int gg = rd * G + g;
+    const int off = tile_off(g + 1, len);
+    tile_copy_async<WAVES>(wpack + off, (gg & 1) ? s_w0 : s_w1, len, wave, lane);
+    return (gg & 1) ? s_w1 : s_w0;
+  };
+  auto stage_end = [&]() {
+    if (!RESIDENT) {
+      tile_copy_wait();
+      __syncthreads();
+    }
+  };
+
+  const int total = __builtin_amdgcn_readfirstlane(s_off[NG]);   // >= NG: slot 0 of a group is always kept
+  const int ntiles = (total + 31) >> 5;
+  const int rounds = (ntiles + WAVES - 1) / WAVES;
+  for (int rd = 0; rd < rounds; ++rd) {
+    const int tile = rd * WAVES + wave;
+    if (tile >= ntiles) {                    // wave-uniform: a wave without a tile only keeps the weight stream going
+      if (RESIDENT) break;
+      for (int g = 0; g < G; ++g) {          // the same copies and barriers as the waves that compute
+        stage_begin(rd, g);
+        stage_end();
+      }
+      continue;
+    }
+
+    bf16x8 a0h[S1], a0l[S1];
+    // pooled layer: accumulator register r of this lane holds column cbase + (r & 3) + 8 * (r >> 2) of the list
+    unsigned int cut = 0;                    // bit r: that column may be of another group than register r - 1's (or is past the end)
+    const int cbase = tile * kNS + 4 * h;
+    int rkey[16];                            // group of register r's column, -1 past the end of the list
+    int g_first;                             // group of the tile's first column
+    bool uni;                                // the tile is 32 columns of ONE group: pooled like a dense tile
+    {
+      const int ei = tile * kNS + col < total ? tile * kNS + col : total - 1;
+      const int ent = s_list[ei];
+      const int j = ent >> 16, p = ent & 0xFFFF;                 // j = o * npoint + group of the object
+      const int o = OBJS > 1 ? j / npoint : 0;
+      const float *fo = s_feat + o * CF * n + p;
+      const float *xo = s_xyz + (o * n + p) * 3;
+      const float *co = s_ctr + j * 3;
+#pragma unroll
+      for (int s = 0; s < S1; ++s) {
+        f32x8 v;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const int k = slot_channel16(s, e, h);
+          float x;
+          if (slot_channel16(s, e, 0) >= 3 && slot_channel16(s, e, 1) < CIN) {
+            x = fo[(k - 3) * n];
+          } else {
+            x = 0.f;
+            if (k < 3) x = xo[k] - co[k];
+            else if (k < CIN) x = fo[(k - 3) * n];
+          }
+          v[e] = x;
+        }
+        split8(v, a0h[s], a0l[s]);
+      }
+      // where the group changes along the tile: one ballot over the columns (= lanes), no LDS traffic
+      const int key = tile * kNS + col < total ? j : -1;
+      const int left = __shfl_up(key, 1, 64);
+      const unsigned int edges = (unsigned int)__ballot(col > 0 && key != left);     // bit c: column c starts a run
+      g_first = __builtin_amdgcn_readfirstlane(j);
+      uni = edges == 0 && tile * kNS + kNS - 1 < total;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {         // every lane active here: the key of column c + 4 h sits in that lane
+        const int c = (r & 3) + 8 * (r >> 2);
+        const int k0 = __builtin_amdgcn_readlane(key, c), k1 = __builtin_amdgcn_readlane(key, c + 4);
+        rkey[r] = h ? k1 : k0;
+      }
+      const unsigned int eh = edges >> (4 * h);
+#pragma unroll
+      for (int r = 1; r < 16; ++r) {
+        // register r - 1 holds the column before this one, or (r & 3 == 0) the one five before it
+        const unsigned int m = (r & 3) ? (eh >> ((r & 3) + 8 * (r >> 2))) & 1u : (eh >> (8 * (r >> 2) - 4)) & 0x1Fu;
+        if (m) cut |= 1u << r;
+      }
+    }
+    bf16x8 a1h[S2], a1l[S2], a2h[S3], a2l[S3];
+    auto split_tile = [&](const f32x16 &acc, bf16x8 &h0, bf16x8 &l0, bf16x8 &h1, bf16x8 &l1) {
+      f32x8 v0, v1;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { v0[e] = relu1(acc[e]); v1[e] = relu1(acc[8 + e]); }
+      split8(v0, h0, l0);
+      split8(v1, h1, l1);
+    };
+    // transposed last layer: lane = output channel, registers (+ the other half of the wave) = the 32 columns
+    auto pool_tile = [&](const f32x16 &acc, int mt) {
+      int *row = s_out + mt * 32 + col;
+      if (uni) {
+        float m0 = fmaxf(fmaxf(acc[0], acc[1]), fmaxf(acc[2], acc[3]));
+        float m1 = fmaxf(fmaxf(acc[4], acc[5]), fmaxf(acc[6], acc[7]));
+        float m2 = fmaxf(fmaxf(acc[8], acc[9]), fmaxf(acc[10], acc[11]));
+        float m3 = fmaxf(fmaxf(acc[12], acc[13]), fmaxf(acc[14], acc[15]));
+        float m = fmaxf(fmaxf(m0, m1), fmaxf(m2, m3));
+        m = fmaxf(m, __shfl_xor(m, 32, 64));
+        if (lane < 32) atomicMax(row + g_first * OLD, __float_as_int(m));
+        return;
+      }
+      auto fold = [&](int r, float m) {      // the run that ends with register r -> its group's pooled row
+        if (rkey[r] >= 0) atomicMax(row + rkey[r] * OLD, __float_as_int(m));
+      };
+      float m = acc[0];
+#pragma unroll
+      for (int r = 1; r < 16; ++r) {
+        if ((cut >> r) & 1u) {
+          fold(r - 1, m);
+          m = acc[r];
+        } else {
+          m = fmaxf(m, acc[r]);
+        }
+      }
+      fold(15, m);
+    };
+    int g = 0;
+    f32x16 prev;
+#pragma unroll
+    for (int mt = 0; mt < M1; ++mt, ++g) {
+      const float *wt = stage_begin(rd, g);
+      const f32x16 acc = mfma_tile16<S1, false, NPROD>(wt, a0h, a0l, lane);
+      if (mt > 0) split_tile(prev, a1h[2 * mt - 2], a1l[2 * mt - 2], a1h[2 * mt - 1], a1l[2 * mt - 1]);
+      prev = acc;
+      stage_end();
+    }
+    split_tile(prev, a1h[2 * M1 - 2], a1l[2 * M1 - 2], a1h[2 * M1 - 1], a1l[2 * M1 - 1]);
+#pragma unroll
+    for (int mt = 0; mt < M2; ++mt, ++g) {
+      const float *wt = stage_begin(rd, g);
+      const f32x16 acc = mfma_tile16<S2, false, NPROD>(wt, a1h, a1l, lane);
+      if (mt > 0) split_tile(prev, a2h[2 * mt - 2], a2l[2 * mt - 2], a2h[2 * mt - 1], a2l[2 * mt - 1]);
+      prev = acc;
+      stage_end();
+    }
+    split_tile(prev, a2h[2 * M2 - 2], a2l[2 * M2 - 2], a2h[2 * M2 - 1], a2l[2 * M2 - 1]);
+#pragma unroll
+    for (int mt = 0; mt < M3; ++mt, ++g) {
+      const float *wt = stage_begin(rd, g);
+      const f32x16 acc = mfma_tile16<S3, true, NPROD>(wt, a2h, a2l, lane);
+      if (mt > 0) pool_tile(prev, mt - 1);
+      prev = acc;
+      stage_end();
+    }
+    pool_tile(prev, M3 - 1);
+  }
+  __syncthreads();
+  // ---- pooled rows out: (object, channel, group) in HBM, [group][channel] here ----------------------------------
+  float *go = out + (size_t)obj0 * C3 * npoint;
+  const int words = nobj * C3 * npoint;
+  if ((npoint & 3) == 0) {
+    float4 *g4 = reinterpret_cast<float4 *>(go);
+    for (int e4 = tid; e4 < words >> 2; e4 += BLOCK) {
+      const int e = e4 << 2, oc = e / npoint, j = e - oc * npoint;     // oc = o * C3 + c
+      const int o = OBJS > 1 ? oc / C3 : 0, c = oc - o * C3;
+      const int *src = s_out + (o * npoint + j) * OLD + c;
+      g4[e4] = make_float4(__int_as_float(src[0]), __int_as_float(src[OLD]), __int_as_float(src[2 * OLD]),
+                           __int_as_float(src[3 * OLD]));
+    }
+  } else {
+    for (int e = tid; e < words; e += BLOCK) {
+      const int oc = e / npoint, j = e - oc * npoint;
+      const int o = OBJS > 1 ? oc / C3 : 0, c = oc - o * C3;
+      go[e] = __int_as_float(s_out[(o * npoint + j) * OLD + c]);
+    }
+  }
+}
+
+template <int CF, int C1, int C2, int C3, int OBJS, bool RESIDENT>
+size_t distinct_lds_bytes(int n, int npoint) {
+  constexpr int CIN = 3 + CF;
+  constexpr int T1 = tile_floats16(CIN), T2 = tile_floats16(C1), T3 = tile_floats16(C2);
+  constexpr int TMAX = T1 > T2 ? (T1 > T3 ? T1 : T3) : (T2 > T3 ? T2 : T3);
+  constexpr int TOTAL = (C1 / 32) * T1 + (C2 / 32) * T2 + (C3 / 32) * T3;
+  constexpr int WBUF = RESIDENT ? TOTAL : 2 * TMAX;
+  const size_t o = OBJS;
+  return sizeof(float) * ((size_t)WBUF + ((o * npoint * (C3 + 1) + 3) & ~(size_t)3) + o * CF * n + o * n * 3 +
+                          o * npoint * 3 + 2 * o * npoint * kNS + o * npoint + 1);
+}
+
 static int g_products = 3;      // 3 = split-bf16 triple product (fp32-accurate, default); 1 = single bf16 product (opt-in)
+// 0 = every launch runs the MLP on all 32 slots; 1 (default) = the streamed-weight form (SA2) runs it on each group's distinct
+// samples only; 2 = so does the resident-weight form (SA1), where it measured slower than the dense kernel
+// (profiles/r8/sa_distinct_bench.txt)
+static int g_distinct = 1;
 
 template <int CF, int C1, int C2, int C3, int WAVES, bool RESIDENT, bool PM, int NPROD>
 int launch_sa_x3_n(int b, int n, int npoint, const float *xyz, const float *new_xyz, const float *feats,
                    const int32_t *idx, const float *wpack, float *out, hipStream_t s, int ld_feat);
 
+// OBJS objects per workgroup when LDS admits them, else fewer; shapes the distinct form cannot hold (its column list and
+// pooled-row pitch need more LDS than the dense form; point / group ids are packed in 16 + 15 bits) run the dense kernel
+template <int CF, int C1, int C2, int C3, int WAVES, bool RESIDENT, bool PM, int NPROD, int OBJS>
+int launch_sa_x3_distinct(int b, int n, int npoint, const float *xyz, const float *new_xyz, const float *feats,
+                          const int32_t *idx, const float *wpack, float *out, hipStream_t s, int ld_feat) {
+  const size_t lds = distinct_lds_bytes<CF, C1, C2, C3, OBJS, RESIDENT>(n, npoint);
+  if (lds > 160 * 1024 || n > 0xFFFF || (long long)OBJS * npoint > 0x7FFF) {
+    if constexpr (OBJS > 1)
+      return launch_sa_x3_distinct<CF, C1, C2, C3, WAVES, RESIDENT, PM, NPROD, OBJS - 1>(b, n, npoint, xyz, new_xyz, feats, idx,
+                                                                                         wpack, out, s, ld_feat);
+    else
+      return launch_sa_x3_n<CF, C1, C2, C3, WAVES, RESIDENT, PM, NPROD>(b, n, npoint, xyz, new_xyz, feats, idx, wpack, out, s, ld_feat);
+  }
+  static size_t attr_lds = 0;
+  if (lds > attr_lds) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(&sa_mlp_x3_distinct_kernel<CF, C1, C2, C3, WAVES, RESIDENT, PM, NPROD, OBJS>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+      return GPS_ERR_LAUNCH;
+    attr_lds = lds;
+  }
+  hipLaunchKernelGGL((sa_mlp_x3_distinct_kernel<CF, C1, C2, C3, WAVES, RESIDENT, PM, NPROD, OBJS>), dim3((b + OBJS - 1) / OBJS),
+                     dim3(WAVES * 64), lds, s, b, n, npoint, xyz, new_xyz, feats, idx, wpack, out, ld_feat, gps::object_extent());
+  return GPS_OK;
+}
+
 template <int CF, int C1, int C2, int C3, int WAVES, bool RESIDENT, bool PM = false>
 int launch_sa_x3(int b, int n, int npoint, const float *xyz, const float *new_xyz, const float *feats,
                  const int32_t *idx, const float *wpack, float *out, hipStream_t s, int ld_feat = 0) {
+  if (g_distinct >= (RESIDENT ? 2 : 1)) {
+    constexpr int OBJS = RESIDENT ? 1 : GPS_SA2_OBJS;
+    return g_products == 1
+               ? launch_sa_x3_distinct<CF, C1, C2, C3, WAVES, RESIDENT, PM, 1, OBJS>(b, n, npoint, xyz, new_xyz, feats, idx, wpack, out, s, ld_feat)
+               : launch_sa_x3_distinct<CF, C1, C2, C3, WAVES, RESIDENT, PM, 3, OBJS>(b, n, npoint, xyz, new_xyz, feats, idx, wpack, out, s, ld_feat);
+  }
   return g_products == 1
              ? launch_sa_x3_n<CF, C1, C2, C3, WAVES, RESIDENT, PM, 1>(b, n, npoint, xyz, new_xyz, feats, idx, wpack, out, s, ld_feat)
              : launch_sa_x3_n<CF, C1, C2, C3, WAVES, RESIDENT, PM, 3>(b, n, npoint, xyz, new_xyz, feats, idx, wpack, out, s, ld_feat);
@@ -695,6 +1054,12 @@ int gps_sa_mlp_pack_layer(int c_in, int c_out, const float *w, const float *shif
 int gps_sa_mlp_set_products(int n) {
   const int was = gps_sa::x3::g_products;
   if (n == 1 || n == 3) gps_sa::x3::g_products = n;
+  return was;
+}
+
+int gps_sa_mlp_set_distinct(int on) {
+  const int was = gps_sa::x3::g_distinct;
+  if (on >= 0 && on <= 2) gps_sa::x3::g_distinct = on;
   return was;
 }
 

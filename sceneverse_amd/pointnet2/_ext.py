@@ -322,6 +322,13 @@ def sa_mlp_pack(weights, shifts, precision: str = "fp32") -> torch.Tensor:
     return buf
 
 
+def sa_mlp_set_distinct(mode: int) -> int:
+    """Which bf16x3 levels run their MLP on each group's distinct samples only (include/gps_hip.h gps_sa_mlp_set_distinct):
+    0 none (the dense kernels: the bit-equality reference and the in-process A/B), 1 the streamed-weight level (SA2; the
+    default), 2 every level.  -> the previous setting."""
+    return int(_native.load().gps_sa_mlp_set_distinct(int(mode)))
+
+
 def sa_mlp_point_major_supported(c_feat: int, channels, nsample: int, precision: str) -> bool:
     return precision == "bf16x3" and c_feat == 3 and list(channels) == [64, 64, 128] and nsample == 32
 
@@ -350,7 +357,7 @@ def sa_mlp_forward(xyz: torch.Tensor, new_xyz: torch.Tensor, features: torch.Ten
         _same_device(xyz, new_xyz, features, idx, wpack)
         out = torch.empty((b, c3, npoint), dtype=torch.float32, device=xyz.device)
         algo = 4 * (b * 3 * n + b * 3 * npoint + b * c_feat * n + b * npoint * nsample + b * c3 * npoint)
-        flops = 2 * b * npoint * nsample * ((3 + c_feat) * c1 + c1 * c2 + c2 * c3)
+        flops = 2 * b * npoint * nsample * ((3 + c_feat) * c1 + c1 * c2 + c2 * c3)      # dense count: see below
         with torch.cuda.device(xyz.device), _timed(f"sa_mlp_forward(c={c_feat},n={n},np={npoint},mlp={c1}-{c2}-{c3},{precision})",
                                                     algo, 3 * flops, "bf16"):
             st = _native.load().gps_sa_mlp_forward_bf16x3_pm(b, n, npoint, nsample, c_feat, c1, c2, c3, xyz.data_ptr(),
@@ -369,6 +376,9 @@ def sa_mlp_forward(xyz: torch.Tensor, new_xyz: torch.Tensor, features: torch.Ten
     # pooled output written once.  (The unfused reference API moves 8x more for the same work -- two group_points
     # outputs and three conv / BN / ReLU round trips -- which is what fusing removes, not this kernel's roof.)
     algo = 4 * (b * 3 * n + b * 3 * npoint + b * c_feat * n + b * npoint * nsample + b * c3 * npoint)
+    # FLOPs: the reference's DENSE count (every one of the nsample slots of every group through the three layers) -- the
+    # algorithmic numerator.  With sa_mlp_set_distinct (SA2 by default) the kernel skips the columns that repeat a group's slot 0,
+    # so flops / time over the MFMA peak is a roof fraction of the algorithm, NOT the occupancy of the matrix pipe.
     flops = 2 * b * npoint * nsample * ((3 + c_feat) * c1 + c1 * c2 + c2 * c3)
     x3 = precision == "bf16x3"
     fn = _native.load().gps_sa_mlp_forward_bf16x3 if x3 else _native.load().gps_sa_mlp_forward
