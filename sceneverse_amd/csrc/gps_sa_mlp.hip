@@ -30,6 +30,11 @@
 //     compact column list in LDS, several objects per workgroup and a segmented max-pool (sa_mlp_x3_distinct_kernel;
 //     gps_sa_mlp_set_distinct).  The dense kernels below stay as the reference and as the resident-weight level (SA1).
 //
+// What the three kernels share is stated once: Geometry (steps, tile sizes and counts of a (CF, C1, C2, C3) MLP), Layout
+// (the LDS carve-up, read by the kernel for its pointers and by the host for its byte count), stage_objects, WeightStream
+// and copy_out_dense; the two split-bf16 kernels also share gather_layer1, split_tile, group_max and mlp_tile (the
+// three-layer walk over one 32-column tile, pooling passed in).
+//
 // K-slot order.  For v_mfma_f32_32x32x2_f32 lane l holds A[i = l&31][k = l>>5], B[k = l>>5][j = l&31]
 // and D[row = (r&3) + 8*(r>>2) + 4*(l>>5)][col = l&31] in register r.  Input channels are therefore
 // consumed in "slots" (it, r): the step for slot (it, r) multiplies channel it*32 + (r&3) + 8*(r>>2)
@@ -153,64 +158,158 @@ __device__ __forceinline__ void tile_copy_async(const float *__restrict__ src, f
 __device__ __forceinline__ void tile_copy_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 // ------------------------------------------------------------------------------------------
+// What the fp32 kernel and the two split-bf16 kernels have in common.
+// ------------------------------------------------------------------------------------------
+// Layer geometry of a (CF -> C1 -> C2 -> C3) MLP in one packed form: STEPS(c_in) = K steps of a layer, TILE(c_in) = floats
+// of one packed 32-row output tile of it (layer_steps / tile_floats here, x3::steps16 / x3::tile_floats16 below).
+template <int CF_, int C1_, int C2_, int C3_, int (*STEPS)(int), int (*TILE)(int)>
+struct Geometry {
+  static_assert(C1_ % 32 == 0 && C2_ % 32 == 0 && C3_ % 32 == 0, "whole 32-row output tiles");
+  static constexpr int CF = CF_, C1 = C1_, C2 = C2_, C3 = C3_, CIN = 3 + CF_;
+  static constexpr int S1 = STEPS(CIN), S2 = STEPS(C1), S3 = STEPS(C2);
+  static constexpr int T1 = TILE(CIN), T2 = TILE(C1), T3 = TILE(C2);
+  static constexpr int M1 = C1 / 32, M2 = C2 / 32, M3 = C3 / 32;
+  static constexpr int TMAX = T1 > T2 ? (T1 > T3 ? T1 : T3) : (T2 > T3 ? T2 : T3);
+  static constexpr int TOTAL = M1 * T1 + M2 * T2 + M3 * T3;   // floats of wpack = [layer 1 tiles | layer 2 tiles | layer 3 tiles]
+  static constexpr int G = M1 + M2 + M3;                      // weight tiles (stages) per round
+  // offset (floats) in wpack of weight tile g (mod G), and its length
+  static __device__ __forceinline__ int tile_off(int g, int &len) {
+    if (g >= G) g -= G;
+    if (g < M1) { len = T1; return g * T1; }
+    if (g < M1 + M2) { len = T2; return M1 * T1 + (g - M1) * T2; }
+    len = T3;
+    return M1 * T1 + M2 * T2 + (g - M1 - M2) * T3;
+  }
+};
+
+// The carve-up of dynamic LDS, offsets in floats.  The kernel takes its pointers from Layout<..., int>, the host its byte
+// count from Layout<..., size_t>::bytes(): no size is written down apart from this list.  OBJS objects per workgroup;
+//   DISTINCT = false (fp32 and dense split-bf16 kernels, OBJS = 1): pooled features [C3][npoint], as they go to HBM;
+//   DISTINCT = true: pooled rows [group][channel] of bit patterns with a pitch of C3 + 1 words (why: the distinct kernel's
+//   header), the list of kept columns and the groups' offsets into it.
+template <class GEO, bool RESIDENT, int OBJS, bool DISTINCT, typename I>
+struct Layout {
+  static constexpr int WBUF = RESIDENT ? GEO::TOTAL : 2 * GEO::TMAX;   // the whole wpack, or buffers w0 (at 0) and w1 (at TMAX)
+  static constexpr int OLD = GEO::C3 + 1;                              // pitch of a pooled row (DISTINCT)
+  I out, feat, xyz, ctr, idx, list, off, end;
+  __host__ __device__ Layout(I n, I npoint) {
+    const I groups = OBJS * npoint;
+    out = WBUF;                                                        // [C3][npoint] | [groups][OLD]
+    feat = out + (DISTINCT ? (groups * OLD + 3) & ~(I)3 : GEO::C3 * npoint);   // [OBJS][CF][n]  (channel-major, 16-byte aligned)
+    xyz = feat + OBJS * GEO::CF * n;                                   // [OBJS][n][3]
+    ctr = xyz + OBJS * n * 3;                                          // [groups][3]
+    idx = ctr + groups * 3;                                            // [groups][32] int32
+    list = idx + groups * kNS;                                         // [groups * 32] kept columns: group << 16 | point
+    off = list + (DISTINCT ? groups * kNS : 0);                        // [groups + 1] first list entry of a group
+    end = off + (DISTINCT ? groups + 1 : 0);
+  }
+  size_t bytes() const { return sizeof(float) * (size_t)end; }
+};
+
+// Stage `nobj` consecutive objects, the first obj0, into LDS: features ([o][CF][n], channel-major as in HBM; PM: they arrive
+// point-major, feats[(obj * n + p) * ld_feat + c], and are transposed on the way), xyz, centres, idx.  OBJS = 1 where nobj is.
+template <int CF, bool PM, int OBJS, int BLOCK>
+__device__ __forceinline__ void stage_objects(int obj0, int nobj, int n, int npoint, const float *__restrict__ xyz,
+                                              const float *__restrict__ new_xyz, const float *__restrict__ feats,
+                                              const int32_t *__restrict__ idx, int ld_feat, float *s_feat, float *s_xyz,
+                                              float *s_ctr, int32_t *s_idx, int tid) {
+  const float *gx = xyz + (size_t)obj0 * n * 3;
+  const float *gc = new_xyz + (size_t)obj0 * npoint * 3;
+  const int32_t *gi = idx + (size_t)obj0 * npoint * kNS;
+  if (PM) {
+    const float *gf = feats + (size_t)obj0 * n * ld_feat;
+    for (int e = tid; e < nobj * CF * n; e += BLOCK) {
+      const int pp = e / CF, c = e - pp * CF;                   // pp = o * n + p
+      const int o = OBJS > 1 ? pp / n : 0;
+      s_feat[o * CF * n + c * n + (pp - o * n)] = gf[(size_t)pp * ld_feat + c];
+    }
+  } else {
+    const float *gf = feats + (size_t)obj0 * CF * n;
+    if (((CF * n) & 3) == 0) {
+      const float4 *g4 = reinterpret_cast<const float4 *>(gf);
+      float4 *l4 = reinterpret_cast<float4 *>(s_feat);
+      for (int e = tid; e < (nobj * CF * n) >> 2; e += BLOCK) l4[e] = g4[e];
+    } else {
+      for (int e = tid; e < nobj * CF * n; e += BLOCK) s_feat[e] = gf[e];
+    }
+  }
+  for (int e = tid; e < nobj * n * 3; e += BLOCK) s_xyz[e] = gx[e];
+  for (int e = tid; e < nobj * npoint * 3; e += BLOCK) s_ctr[e] = gc[e];
+  for (int e = tid; e < nobj * npoint * kNS; e += BLOCK) s_idx[e] = gi[e];
+}
+
+// The weight tiles of wpack, one per stage g of a round rd.  RESIDENT: the whole wpack sits in LDS after first(), a stage
+// is an offset.  Otherwise the 32-row tiles stream through the double buffer w0 / w1: g counts the stages of a round, gg
+// all stages so far; tile gg sits in buffer gg & 1 and begin() starts the copy of the next tile into the other one (G may
+// be odd, so the parity carries over rounds), end() is that copy's wait and the workgroup's one barrier per tile.
+template <class GEO, int WAVES, bool RESIDENT>
+struct WeightStream {
+  const float *wpack;
+  float *s_w0;
+  int wave, lane;
+  __device__ __forceinline__ void first() const {               // completion: tile_copy_wait() + barrier, by the caller
+    tile_copy_async<WAVES>(wpack, s_w0, RESIDENT ? GEO::TOTAL : GEO::T1, wave, lane);
+  }
+  __device__ __forceinline__ const float *begin(int rd, int g) const {   // -> the LDS tile to compute on
+    int len;
+    if (RESIDENT) return s_w0 + GEO::tile_off(g, len);
+    const int gg = rd * GEO::G + g;
+    const int off = GEO::tile_off(g + 1, len);
+    float *s_w1 = s_w0 + GEO::TMAX;
+    tile_copy_async<WAVES>(wpack + off, (gg & 1) ? s_w0 : s_w1, len, wave, lane);
+    return (gg & 1) ? s_w1 : s_w0;
+  }
+  __device__ __forceinline__ void end() const {
+    if (!RESIDENT) {
+      tile_copy_wait();
+      __syncthreads();
+    }
+  }
+};
+
+// pooled features [C3][npoint] of one object out, coalesced
+template <int BLOCK>
+__device__ __forceinline__ void copy_out_dense(const float *s_out, float *go, int total, int tid) {
+  if ((total & 3) == 0) {
+    const float4 *l4 = reinterpret_cast<const float4 *>(s_out);
+    float4 *g4 = reinterpret_cast<float4 *>(go);
+    for (int e = tid; e < total >> 2; e += BLOCK) g4[e] = l4[e];
+  } else {
+    for (int e = tid; e < total; e += BLOCK) go[e] = s_out[e];
+  }
+}
+
+// ------------------------------------------------------------------------------------------
 // fused SA level: ball-query indices in, pooled features out.
 //   xyz (b,n,3), new_xyz (b,npoint,3), feats (b,CF,n), idx (b,npoint,32) -> out (b,C3,npoint)
 //   wpack = [layer 1 tiles | layer 2 tiles | layer 3 tiles]
 // ------------------------------------------------------------------------------------------
+template <int CF, int C1, int C2, int C3>
+using GeometryF32 = Geometry<CF, C1, C2, C3, layer_steps, tile_floats>;
+
 template <int CF, int C1, int C2, int C3>
 __global__ __launch_bounds__(kBlock, 2) void sa_mlp_kernel(
     int b, int n, int npoint, const float *__restrict__ xyz, const float *__restrict__ new_xyz,
     const float *__restrict__ feats, const int32_t *__restrict__ idx,
     const float *__restrict__ wpack, float *__restrict__ out, const int *__restrict__ n_obj_dev) {
   if (n_obj_dev && (int)blockIdx.x >= *n_obj_dev) return;      // object extent: nothing read or written
-  constexpr int CIN = 3 + CF;
-  constexpr int S1 = layer_steps(CIN), S2 = C1 / 2, S3 = C2 / 2;
-  constexpr int T1 = tile_floats(CIN), T2 = tile_floats(C1), T3 = tile_floats(C2);
-  constexpr int M1 = C1 / 32, M2 = C2 / 32, M3 = C3 / 32;
-  constexpr int TMAX = T1 > T2 ? (T1 > T3 ? T1 : T3) : (T2 > T3 ? T2 : T3);
-  constexpr int G = M1 + M2 + M3;            // weight tiles (stages) per round
+  using GEO = GeometryF32<CF, C1, C2, C3>;
+  constexpr int CIN = GEO::CIN, S1 = GEO::S1, S2 = GEO::S2, S3 = GEO::S3, M1 = GEO::M1, M2 = GEO::M2, M3 = GEO::M3;
 
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  float *s_w0 = lds;                         // TMAX
-  float *s_w1 = s_w0 + TMAX;                 // TMAX
-  float *s_out = s_w1 + TMAX;                // C3 * npoint
-  float *s_feat = s_out + C3 * npoint;       // CF * n   (channel-major, as in HBM)
-  float *s_xyz = s_feat + CF * n;            // n * 3
-  float *s_ctr = s_xyz + n * 3;              // npoint * 3
-  int32_t *s_idx = reinterpret_cast<int32_t *>(s_ctr + npoint * 3);  // npoint * 32
+  const Layout<GEO, false, 1, false, int> L(n, npoint);
+  float *s_out = lds + L.out, *s_feat = lds + L.feat, *s_xyz = lds + L.xyz, *s_ctr = lds + L.ctr;
+  int32_t *s_idx = reinterpret_cast<int32_t *>(lds + L.idx);
 
   const int obj = blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int col = lane & 31, h = lane >> 5;
 
-  // ---- stage the object ------------------------------------------------------------------
-  {
-    const float *gf = feats + (size_t)obj * CF * n;
-    const float *gx = xyz + (size_t)obj * n * 3;
-    const float *gc = new_xyz + (size_t)obj * npoint * 3;
-    const int32_t *gi = idx + (size_t)obj * npoint * kNS;
-    if (((CF * n) & 3) == 0) {
-      const float4 *g4 = reinterpret_cast<const float4 *>(gf);
-      float4 *l4 = reinterpret_cast<float4 *>(s_feat);
-      for (int e = tid; e < (CF * n) >> 2; e += kBlock) l4[e] = g4[e];
-    } else {
-      for (int e = tid; e < CF * n; e += kBlock) s_feat[e] = gf[e];
-    }
-    for (int e = tid; e < n * 3; e += kBlock) s_xyz[e] = gx[e];
-    for (int e = tid; e < npoint * 3; e += kBlock) s_ctr[e] = gc[e];
-    for (int e = tid; e < npoint * kNS; e += kBlock) s_idx[e] = gi[e];
-  }
-  tile_copy_async(wpack, s_w0, T1, wave, lane);
+  stage_objects<CF, false, 1, kBlock>(obj, 1, n, npoint, xyz, new_xyz, feats, idx, 0, s_feat, s_xyz, s_ctr, s_idx, tid);
+  const WeightStream<GEO, kWaves, false> ws{wpack, lds, wave, lane};
+  ws.first();
   tile_copy_wait();
   __syncthreads();
-
-  auto tile_src = [&](int g, int &len) -> const float * {  // packed tile of stage g (mod G)
-    if (g >= G) g -= G;
-    if (g < M1) { len = T1; return wpack + (size_t)g * T1; }
-    if (g < M1 + M2) { len = T2; return wpack + (size_t)M1 * T1 + (size_t)(g - M1) * T2; }
-    len = T3;
-    return wpack + (size_t)M1 * T1 + (size_t)M2 * T2 + (size_t)(g - M1 - M2) * T3;
-  };
 
   const int rounds = (npoint + kWaves - 1) / kWaves;
   for (int rd = 0; rd < rounds; ++rd) {
@@ -243,86 +342,47 @@ __global__ __launch_bounds__(kBlock, 2) void sa_mlp_kernel(
     }
 
     float a1[M1 * 16], a2[M2 * 16];
-    // g = stage within the round; gg = running stage count.  Tile gg sits in buffer gg & 1 and the
-    // next tile is prefetched into the other one (G may be odd, so the parity carries over rounds).
-    int g = 0;
+    int g = 0;                                             // stage within the round
     // ---- layer 1 ----------------------------------------------------------------------------
 #pragma unroll
     for (int mt = 0; mt < M1; ++mt, ++g) {
-      const int gg = rd * G + g;
-      int len;
-      const float *src = tile_src(g + 1, len);
-      tile_copy_async(src, (gg & 1) ? s_w0 : s_w1, len, wave, lane);
-      const f32x16 acc = mfma_tile<S1>((gg & 1) ? s_w1 : s_w0, a0, lane);
+      const f32x16 acc = mfma_tile<S1>(ws.begin(rd, g), a0, lane);
 #pragma unroll
       for (int r = 0; r < 16; ++r) a1[mt * 16 + r] = fmaxf(acc[r], 0.f);
-      tile_copy_wait();
-      __syncthreads();
+      ws.end();
     }
     // ---- layer 2 ----------------------------------------------------------------------------
 #pragma unroll
     for (int mt = 0; mt < M2; ++mt, ++g) {
-      const int gg = rd * G + g;
-      int len;
-      const float *src = tile_src(g + 1, len);
-      tile_copy_async(src, (gg & 1) ? s_w0 : s_w1, len, wave, lane);
-      const f32x16 acc = mfma_tile<S2>((gg & 1) ? s_w1 : s_w0, a1, lane);
+      const f32x16 acc = mfma_tile<S2>(ws.begin(rd, g), a1, lane);
 #pragma unroll
       for (int r = 0; r < 16; ++r) a2[mt * 16 + r] = fmaxf(acc[r], 0.f);
-      tile_copy_wait();
-      __syncthreads();
+      ws.end();
     }
     // ---- layer 3 + max over the 32 samples ---------------------------------------------------
     for (int mt = 0; mt < M3; ++mt, ++g) {
-      const int gg = rd * G + g;
-      int len;
-      const float *src = tile_src(g + 1, len);
-      tile_copy_async(src, (gg & 1) ? s_w0 : s_w1, len, wave, lane);
-      const f32x16 acc = mfma_tile<S3>((gg & 1) ? s_w1 : s_w0, a2, lane);
+      const f32x16 acc = mfma_tile<S3>(ws.begin(rd, g), a2, lane);
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const float m = half_wave_max(acc[r]);
         if (col == 31 && live)
           s_out[(mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * npoint + tile] = fmaxf(m, 0.f);
       }
-      tile_copy_wait();
-      __syncthreads();
+      ws.end();
     }
   }
-  // ---- pooled features out, coalesced -----------------------------------------------------------
-  float *go = out + (size_t)obj * C3 * npoint;
-  const int total = C3 * npoint;
-  if ((total & 3) == 0) {
-    const float4 *l4 = reinterpret_cast<const float4 *>(s_out);
-    float4 *g4 = reinterpret_cast<float4 *>(go);
-    for (int e = tid; e < total >> 2; e += kBlock) g4[e] = l4[e];
-  } else {
-    for (int e = tid; e < total; e += kBlock) go[e] = s_out[e];
-  }
-}
-
-template <int CF, int C1, int C2, int C3>
-size_t sa_lds_bytes(int n, int npoint) {
-  constexpr int CIN = 3 + CF;
-  constexpr int T1 = tile_floats(CIN), T2 = tile_floats(C1), T3 = tile_floats(C2);
-  constexpr int TMAX = T1 > T2 ? (T1 > T3 ? T1 : T3) : (T2 > T3 ? T2 : T3);
-  return sizeof(float) * ((size_t)2 * TMAX + (size_t)C3 * npoint + (size_t)CF * n + (size_t)n * 3 +
-                          (size_t)npoint * 3 + (size_t)npoint * kNS);
+  copy_out_dense<kBlock>(s_out, out + (size_t)obj * C3 * npoint, C3 * npoint, tid);
 }
 
 template <int CF, int C1, int C2, int C3>
 int launch_sa(int b, int n, int npoint, const float *xyz, const float *new_xyz, const float *feats,
               const int32_t *idx, const float *wpack, float *out, hipStream_t s) {
-  const size_t lds = sa_lds_bytes<CF, C1, C2, C3>(n, npoint);
+  const size_t lds = Layout<GeometryF32<CF, C1, C2, C3>, false, 1, false, size_t>(n, npoint).bytes();
   if (lds > 80 * 1024) return GPS_ERR_UNSUPPORTED;   // keep two workgroups per CU
-  static gps_dev::PerDevice<bool, 1> attr_dev;          // dynamic LDS above 64 KiB needs opting in, per device
-  bool &attr_set = attr_dev.row()[0];
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(&sa_mlp_kernel<CF, C1, C2, C3>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) != hipSuccess)
-      return GPS_ERR_LAUNCH;
-    attr_set = true;
-  }
+  static gps_dev::PerDevice<size_t, 1> granted;
+  const int st = gps_dev::grant_lds(reinterpret_cast<const void *>(&sa_mlp_kernel<CF, C1, C2, C3>), lds, 80 * 1024,
+                                    granted.row()[0]);
+  if (st != GPS_OK) return st;
   hipLaunchKernelGGL((sa_mlp_kernel<CF, C1, C2, C3>), dim3(b), dim3(kBlock), lds, s, b, n, npoint, xyz,
                      new_xyz, feats, idx, wpack, out, gps::object_extent());
   return GPS_OK;
@@ -354,6 +414,8 @@ __host__ __device__ constexpr int slot_channel16(int it_u, int e, int h) {   // 
 __host__ __device__ constexpr int tile_floats16(int c_in) {
   return (steps16(c_in) * 512 + 32 + 255) / 256 * 256;
 }
+template <int CF, int C1, int C2, int C3>
+using Geometry16 = Geometry<CF, C1, C2, C3, steps16, tile_floats16>;
 
 __device__ __forceinline__ uint16_t f2bf(float f) {
   unsigned int u = __float_as_uint(f);
@@ -455,6 +517,98 @@ __device__ __forceinline__ f32x16 mfma_tile16(const float *__restrict__ tile, co
   return acc;
 }
 
+// Layer-1 B operand of one column (= this lane's, both halves of the wave), split: channel k < 3 is xo[k] - co[k] (the
+// point's xyz row minus its group's centre row), channel k >= 3 is fo[(k - 3) * n] (fo = the object's channel-major
+// features at the point), zero from CIN on.  Slots whose 8 channels are all features skip the per-lane decision.
+template <class GEO>
+__device__ __forceinline__ void gather_layer1(const float *fo, int n, const float *xo, const float *co, int h,
+                                              bf16x8 (&a0h)[GEO::S1], bf16x8 (&a0l)[GEO::S1]) {
+#pragma unroll
+  for (int s = 0; s < GEO::S1; ++s) {
+    f32x8 v;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int k = slot_channel16(s, e, h);
+      float x;
+      if (slot_channel16(s, e, 0) >= 3 && slot_channel16(s, e, 1) < GEO::CIN) {
+        x = fo[(k - 3) * n];
+      } else {
+        x = 0.f;
+        if (k < 3) x = xo[k] - co[k];
+        else if (k < GEO::CIN) x = fo[(k - 3) * n];
+      }
+      v[e] = x;
+    }
+    split8(v, a0h[s], a0l[s]);
+  }
+}
+
+// ReLU + hi/lo split of one 32-row output tile = two K steps of the next layer
+__device__ __forceinline__ void split_tile(const f32x16 &acc, bf16x8 &h0, bf16x8 &l0, bf16x8 &h1, bf16x8 &l1) {
+  f32x8 v0, v1;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) { v0[e] = relu1(acc[e]); v1[e] = relu1(acc[8 + e]); }
+  split8(v0, h0, l0);
+  split8(v1, h1, l1);
+}
+
+// A last-layer tile whose 32 columns are ONE group: lane = output channel, registers (+ the other half of the wave) = the
+// 32 samples -> max-pool = 15 in-lane max + one cross-half exchange
+__device__ __forceinline__ float group_max(const f32x16 &acc) {
+  float m0 = fmaxf(fmaxf(acc[0], acc[1]), fmaxf(acc[2], acc[3]));
+  float m1 = fmaxf(fmaxf(acc[4], acc[5]), fmaxf(acc[6], acc[7]));
+  float m2 = fmaxf(fmaxf(acc[8], acc[9]), fmaxf(acc[10], acc[11]));
+  float m3 = fmaxf(fmaxf(acc[12], acc[13]), fmaxf(acc[14], acc[15]));
+  const float m = fmaxf(fmaxf(m0, m1), fmaxf(m2, m3));
+  return fmaxf(m, __shfl_xor(m, 32, 64));
+}
+
+// The three layers over one 32-column tile, stages 0 .. G-1 of round rd of the weight stream; the last layer runs in the
+// transposed form (lane = output channel) and hands each of its M3 tiles to pool(acc, mt).
+// Software pipeline: the post-processing (ReLU + hi/lo split, or the pooling) of output tile mt-1 is issued after the
+// MFMAs of tile mt, in the same scheduling region, so that its VALU work runs in the shadow of the matrix pipe
+// (independent registers).  Only the last tile of a layer is post-processed in the open (the next layer needs all of it).
+// pool is taken by value and must capture by value: through references the compiler re-reads what it captured after
+// every LDS atomic of the distinct form and works out the run masks again for each of the M3 tiles (measured at SA2 on
+// the workload's clouds: 237 us against 228, profiles/r9/sa_mlp_refactor.txt).
+template <class GEO, int NPROD, class STREAM, class POOL>
+__device__ __forceinline__ void mlp_tile(const STREAM &ws, int rd, const bf16x8 (&a0h)[GEO::S1], const bf16x8 (&a0l)[GEO::S1],
+                                         int lane, POOL pool) {
+  constexpr int S1 = GEO::S1, S2 = GEO::S2, S3 = GEO::S3, M1 = GEO::M1, M2 = GEO::M2, M3 = GEO::M3;
+  bf16x8 a1h[S2], a1l[S2], a2h[S3], a2l[S3];
+  int g = 0;
+  f32x16 prev;
+#pragma unroll
+  for (int mt = 0; mt < M1; ++mt, ++g) {
+    const float *wt = ws.begin(rd, g);
+    const f32x16 acc = mfma_tile16<S1, false, NPROD>(wt, a0h, a0l, lane);
+    if (mt > 0) split_tile(prev, a1h[2 * mt - 2], a1l[2 * mt - 2], a1h[2 * mt - 1], a1l[2 * mt - 1]);
+    prev = acc;
+    ws.end();
+  }
+  split_tile(prev, a1h[2 * M1 - 2], a1l[2 * M1 - 2], a1h[2 * M1 - 1], a1l[2 * M1 - 1]);
+#pragma unroll
+  for (int mt = 0; mt < M2; ++mt, ++g) {
+    const float *wt = ws.begin(rd, g);
+    const f32x16 acc = mfma_tile16<S2, false, NPROD>(wt, a1h, a1l, lane);
+    if (mt > 0) split_tile(prev, a2h[2 * mt - 2], a2l[2 * mt - 2], a2h[2 * mt - 1], a2l[2 * mt - 1]);
+    prev = acc;
+    ws.end();
+  }
+  split_tile(prev, a2h[2 * M2 - 2], a2l[2 * M2 - 2], a2h[2 * M2 - 1], a2l[2 * M2 - 1]);
+  // unrolled for both kernels: rolled, the distinct form measured 770 us against 742 with every group full at SA2, and
+  // the dense rows are within their spread either way (profiles/r9/sa_mlp_refactor.txt)
+#pragma unroll
+  for (int mt = 0; mt < M3; ++mt, ++g) {
+    const float *wt = ws.begin(rd, g);
+    const f32x16 acc = mfma_tile16<S3, true, NPROD>(wt, a2h, a2l, lane);
+    if (mt > 0) pool(prev, mt - 1);
+    prev = acc;
+    ws.end();
+  }
+  pool(prev, M3 - 1);
+}
+
 // WAVES waves per workgroup (each owns one 32-sample group per round).  RESIDENT: the whole packed
 // MLP fits in LDS next to the object -> loaded once per workgroup, no per-tile barriers; otherwise
 // the 32-row weight tiles stream through a double buffer (one barrier per tile).  More waves per
@@ -469,79 +623,22 @@ __global__ __launch_bounds__(WAVES * 64) void sa_mlp_x3_kernel(
     const float *__restrict__ feats, const int32_t *__restrict__ idx,
     const float *__restrict__ wpack, float *__restrict__ out, int ld_feat, const int *__restrict__ n_obj_dev) {
   if (n_obj_dev && (int)blockIdx.x >= *n_obj_dev) return;      // object extent: nothing read or written
+  using GEO = Geometry16<CF, C1, C2, C3>;
   constexpr int BLOCK = WAVES * 64;
-  constexpr int CIN = 3 + CF;
-  constexpr int S1 = steps16(CIN), S2 = C1 / 16, S3 = C2 / 16;
-  constexpr int T1 = tile_floats16(CIN), T2 = tile_floats16(C1), T3 = tile_floats16(C2);
-  constexpr int M1 = C1 / 32, M2 = C2 / 32, M3 = C3 / 32;
-  constexpr int TMAX = T1 > T2 ? (T1 > T3 ? T1 : T3) : (T2 > T3 ? T2 : T3);
-  constexpr int TOTAL = M1 * T1 + M2 * T2 + M3 * T3;
-  constexpr int G = M1 + M2 + M3;
-  constexpr int WBUF = RESIDENT ? TOTAL : 2 * TMAX;
 
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  float *s_w0 = lds;
-  float *s_w1 = s_w0 + TMAX;                 // streaming form only
-  float *s_out = lds + WBUF;                 // C3 * npoint
-  float *s_feat = s_out + C3 * npoint;       // CF * n
-  float *s_xyz = s_feat + CF * n;            // n * 3
-  float *s_ctr = s_xyz + n * 3;              // npoint * 3
-  int32_t *s_idx = reinterpret_cast<int32_t *>(s_ctr + npoint * 3);
+  const Layout<GEO, RESIDENT, 1, false, int> L(n, npoint);
+  float *s_out = lds + L.out, *s_feat = lds + L.feat, *s_xyz = lds + L.xyz, *s_ctr = lds + L.ctr;
+  int32_t *s_idx = reinterpret_cast<int32_t *>(lds + L.idx);
 
   const int obj = blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int col = lane & 31, h = lane >> 5;
-  {
-    const float *gx = xyz + (size_t)obj * n * 3;
-    const float *gc = new_xyz + (size_t)obj * npoint * 3;
-    const int32_t *gi = idx + (size_t)obj * npoint * kNS;
-    if (PM) {
-      const float *gf = feats + (size_t)obj * n * ld_feat;
-      for (int e = tid; e < CF * n; e += BLOCK) {
-        const int p = e / CF, c = e - p * CF;
-        s_feat[c * n + p] = gf[(size_t)p * ld_feat + c];
-      }
-    } else {
-      const float *gf = feats + (size_t)obj * CF * n;
-      if (((CF * n) & 3) == 0) {
-        const float4 *g4 = reinterpret_cast<const float4 *>(gf);
-        float4 *l4 = reinterpret_cast<float4 *>(s_feat);
-        for (int e = tid; e < (CF * n) >> 2; e += BLOCK) l4[e] = g4[e];
-      } else {
-        for (int e = tid; e < CF * n; e += BLOCK) s_feat[e] = gf[e];
-      }
-    }
-    for (int e = tid; e < n * 3; e += BLOCK) s_xyz[e] = gx[e];
-    for (int e = tid; e < npoint * 3; e += BLOCK) s_ctr[e] = gc[e];
-    for (int e = tid; e < npoint * kNS; e += BLOCK) s_idx[e] = gi[e];
-  }
-  tile_copy_async<WAVES>(wpack, s_w0, RESIDENT ? TOTAL : T1, wave, lane);
+  stage_objects<CF, PM, 1, BLOCK>(obj, 1, n, npoint, xyz, new_xyz, feats, idx, ld_feat, s_feat, s_xyz, s_ctr, s_idx, tid);
+  const WeightStream<GEO, WAVES, RESIDENT> ws{wpack, lds, wave, lane};
+  ws.first();
   tile_copy_wait();
   __syncthreads();
-
-  auto tile_off = [&](int g, int &len) -> int {      // offset (floats) of weight tile g (mod G)
-    if (g >= G) g -= G;
-    if (g < M1) { len = T1; return g * T1; }
-    if (g < M1 + M2) { len = T2; return M1 * T1 + (g - M1) * T2; }
-    len = T3;
-    return M1 * T1 + M2 * T2 + (g - M1 - M2) * T3;
-  };
-  // begin stage g of round rd: returns the LDS tile to compute on; streaming form also starts the
-  // copy of the next tile into the other buffer
-  auto stage_begin = [&](int rd, int g) -> const float * {
-    int len;
-    if (RESIDENT) return s_w0 + tile_off(g, len);
-    const int gg = rd * G + g;
-    const int off = tile_off(g + 1, len);
-    tile_copy_async<WAVES>(wpack + off, (gg & 1) ? s_w0 : s_w1, len, wave, lane);
-    return (gg & 1) ? s_w1 : s_w0;
-  };
-  auto stage_end = [&]() {
-    if (!RESIDENT) {
-      tile_copy_wait();
-      __syncthreads();
-    }
-  };
 
   const int rounds = (npoint + WAVES - 1) / WAVES;
   for (int rd = 0; rd < rounds; ++rd) {
@@ -549,90 +646,16 @@ __global__ __launch_bounds__(WAVES * 64) void sa_mlp_x3_kernel(
     const bool live = tile < npoint;
     const int j = live ? tile : npoint - 1;
 
-    bf16x8 a0h[S1], a0l[S1];
-    {
-      const int p = s_idx[j * kNS + col];
-#pragma unroll
-      for (int s = 0; s < S1; ++s) {
-        f32x8 v;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const int k = slot_channel16(s, e, h);
-          float x;
-          if (slot_channel16(s, e, 0) >= 3 && slot_channel16(s, e, 1) < CIN) {
-            x = s_feat[(k - 3) * n + p];
-          } else {
-            x = 0.f;
-            if (k < 3) x = s_xyz[p * 3 + k] - s_ctr[j * 3 + k];
-            else if (k < CIN) x = s_feat[(k - 3) * n + p];
-          }
-          v[e] = x;
-        }
-        split8(v, a0h[s], a0l[s]);
-      }
-    }
-    bf16x8 a1h[S2], a1l[S2], a2h[S3], a2l[S3];
-    // Software pipeline: the post-processing (ReLU + hi/lo split, or ReLU + max-pool) of output tile
-    // mt-1 is issued after the MFMAs of tile mt, in the same scheduling region, so that its VALU work
-    // runs in the shadow of the matrix pipe (independent registers).  Only the last tile of a layer
-    // is post-processed in the open (the next layer needs all of it).
-    auto split_tile = [&](const f32x16 &acc, bf16x8 &h0, bf16x8 &l0, bf16x8 &h1, bf16x8 &l1) {
-      f32x8 v0, v1;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) { v0[e] = relu1(acc[e]); v1[e] = relu1(acc[8 + e]); }
-      split8(v0, h0, l0);
-      split8(v1, h1, l1);
-    };
-    // last layer in the transposed form: lane = output channel, registers (+ the other half of the
-    // wave) = the 32 samples of the group -> max-pool = 15 in-lane max + one cross-half exchange
-    auto pool_tile = [&](const f32x16 &acc, int mt) {
-      float m0 = fmaxf(fmaxf(acc[0], acc[1]), fmaxf(acc[2], acc[3]));
-      float m1 = fmaxf(fmaxf(acc[4], acc[5]), fmaxf(acc[6], acc[7]));
-      float m2 = fmaxf(fmaxf(acc[8], acc[9]), fmaxf(acc[10], acc[11]));
-      float m3 = fmaxf(fmaxf(acc[12], acc[13]), fmaxf(acc[14], acc[15]));
-      float m = fmaxf(fmaxf(m0, m1), fmaxf(m2, m3));
-      m = fmaxf(m, __shfl_xor(m, 32, 64));
+    bf16x8 a0h[GEO::S1], a0l[GEO::S1];
+    const int p = s_idx[j * kNS + col];
+    gather_layer1<GEO>(s_feat + p, n, s_xyz + p * 3, s_ctr + j * 3, h, a0h, a0l);
+    mlp_tile<GEO, NPROD>(ws, rd, a0h, a0l, lane, [=](const f32x16 &acc, int mt) {
+      const float m = group_max(acc);
       if (lane < 32 && live) s_out[(mt * 32 + lane) * npoint + tile] = fmaxf(m, 0.f);   // ReLU after the max
-    };
-    int g = 0;
-    f32x16 prev;
-#pragma unroll
-    for (int mt = 0; mt < M1; ++mt, ++g) {
-      const float *wt = stage_begin(rd, g);
-      const f32x16 acc = mfma_tile16<S1, false, NPROD>(wt, a0h, a0l, lane);
-      if (mt > 0) split_tile(prev, a1h[2 * mt - 2], a1l[2 * mt - 2], a1h[2 * mt - 1], a1l[2 * mt - 1]);
-      prev = acc;
-      stage_end();
-    }
-    split_tile(prev, a1h[2 * M1 - 2], a1l[2 * M1 - 2], a1h[2 * M1 - 1], a1l[2 * M1 - 1]);
-#pragma unroll
-    for (int mt = 0; mt < M2; ++mt, ++g) {
-      const float *wt = stage_begin(rd, g);
-      const f32x16 acc = mfma_tile16<S2, false, NPROD>(wt, a1h, a1l, lane);
-      if (mt > 0) split_tile(prev, a2h[2 * mt - 2], a2l[2 * mt - 2], a2h[2 * mt - 1], a2l[2 * mt - 1]);
-      prev = acc;
-      stage_end();
-    }
-    split_tile(prev, a2h[2 * M2 - 2], a2l[2 * M2 - 2], a2h[2 * M2 - 1], a2l[2 * M2 - 1]);
-    for (int mt = 0; mt < M3; ++mt, ++g) {
-      const float *wt = stage_begin(rd, g);
-      const f32x16 acc = mfma_tile16<S3, true, NPROD>(wt, a2h, a2l, lane);
-      if (mt > 0) pool_tile(prev, mt - 1);
-      prev = acc;
-      stage_end();
-    }
-    pool_tile(prev, M3 - 1);
+    });
   }
   if (RESIDENT) __syncthreads();
-  float *go = out + (size_t)obj * C3 * npoint;
-  const int total = C3 * npoint;
-  if ((total & 3) == 0) {
-    const float4 *l4 = reinterpret_cast<const float4 *>(s_out);
-    float4 *g4 = reinterpret_cast<float4 *>(go);
-    for (int e = tid; e < total >> 2; e += BLOCK) g4[e] = l4[e];
-  } else {
-    for (int e = tid; e < total; e += BLOCK) go[e] = s_out[e];
-  }
+  copy_out_dense<BLOCK>(s_out, out + (size_t)obj * C3 * npoint, C3 * npoint, tid);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -640,12 +663,16 @@ __global__ __launch_bounds__(WAVES * 64) void sa_mlp_x3_kernel(
 // it found with the group's first hit, so slot c > 0 with idx[c] == idx[0] is the same point, the same centre and the
 // same MLP column as slot 0: the max-pool cannot see it.  The rule is applied to whatever idx holds (it does not assume
 // that the kept slots form a prefix), so the pooled features are those of the dense kernel above for any idx.
-//   * after staging, the workgroup builds in LDS the list of kept (group, point) columns, group after group (ballot +
-//     prefix count per group, one prefix sum over the groups); one tile = 32 consecutive list entries, the layer-1
-//     operands are gathered per lane from the entry's own point and its own group's centre; tiles past the end of the
-//     list are not computed, lanes past the end of the last tile repeat the last entry and are not pooled;
-//   * a group's columns may straddle tiles and waves: each lane keeps a running max over its registers' runs of equal
-//     group and folds a run into the group's pooled row with an LDS integer max on the bit pattern (rows start at +0,
+// The kernel is the dense one -- the same Geometry, stage_objects, WeightStream, gather_layer1 and mlp_tile -- with another
+// choice of columns and another pooling; what is its own:
+//   * after staging, the workgroup builds in LDS the list of kept (group, point) columns, group after group (scan_groups:
+//     ballot + prefix count per group; one prefix sum over the groups); one tile = 32 consecutive list entries, and
+//     gather_layer1 is given the entry's own point and its own group's centre; tiles past the end of the list are not
+//     computed (a wave without a tile only keeps the weight stream's copies and barriers going), lanes past the end of
+//     the last tile repeat the last entry and are not pooled;
+//   * a group's columns may straddle tiles and waves: a tile of 32 columns of ONE group is pooled like a dense tile
+//     (group_max); otherwise each lane keeps a running max over its registers' runs of equal group (rkey, cut).  Either
+//     way a maximum is folded into the group's pooled row with an LDS integer max on the bit pattern (rows start at +0,
 //     which is also the ReLU after the max; max is order-independent, so the result is deterministic; on the bit pattern
 //     a positive NaN is the largest value and is kept, where the dense form's fmaxf drops it).  The pooled
 //     rows are kept [group][channel] with a pitch of C3 + 1 words: conflict-free for the lanes (= channels) of a fold
@@ -668,60 +695,28 @@ __global__ __launch_bounds__(WAVES * 64) void sa_mlp_x3_distinct_kernel(
   const int obj0 = blockIdx.x * OBJS;
   if (obj0 >= n_obj) return;                                   // object extent: nothing read or written
   const int nobj = n_obj - obj0 < OBJS ? n_obj - obj0 : OBJS;  // objects of this workgroup
+  using GEO = Geometry16<CF, C1, C2, C3>;
+  using LAYOUT = Layout<GEO, RESIDENT, OBJS, true, int>;
   constexpr int BLOCK = WAVES * 64;
-  constexpr int CIN = 3 + CF;
-  constexpr int S1 = steps16(CIN), S2 = C1 / 16, S3 = C2 / 16;
-  constexpr int T1 = tile_floats16(CIN), T2 = tile_floats16(C1), T3 = tile_floats16(C2);
-  constexpr int M1 = C1 / 32, M2 = C2 / 32, M3 = C3 / 32;
-  constexpr int TMAX = T1 > T2 ? (T1 > T3 ? T1 : T3) : (T2 > T3 ? T2 : T3);
-  constexpr int TOTAL = M1 * T1 + M2 * T2 + M3 * T3;
-  constexpr int G = M1 + M2 + M3;
-  constexpr int WBUF = RESIDENT ? TOTAL : 2 * TMAX;
-  constexpr int OLD = C3 + 1;                // pitch of a pooled row
+  constexpr int OLD = LAYOUT::OLD;           // pitch of a pooled row
 
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  float *s_w0 = lds;
-  float *s_w1 = s_w0 + TMAX;                 // streaming form only
-  int *s_out = reinterpret_cast<int *>(lds + WBUF);             // [OBJS * npoint][OLD] bit patterns
-  float *s_feat = lds + WBUF + ((OBJS * npoint * OLD + 3) & ~3);  // [OBJS][CF][n]
-  float *s_xyz = s_feat + OBJS * CF * n;     // [OBJS][n][3]
-  float *s_ctr = s_xyz + OBJS * n * 3;       // [OBJS * npoint][3]
-  int32_t *s_idx = reinterpret_cast<int32_t *>(s_ctr + OBJS * npoint * 3);   // [OBJS * npoint][32]
-  int32_t *s_list = s_idx + OBJS * npoint * kNS;                // kept columns: group << 16 | point
-  int32_t *s_off = s_list + OBJS * npoint * kNS;                // [OBJS * npoint + 1] first list entry of a group
+  const LAYOUT L(n, npoint);
+  int *s_out = reinterpret_cast<int *>(lds + L.out);            // bit patterns
+  float *s_feat = lds + L.feat, *s_xyz = lds + L.xyz, *s_ctr = lds + L.ctr;
+  int32_t *s_idx = reinterpret_cast<int32_t *>(lds + L.idx);
+  int32_t *s_list = reinterpret_cast<int32_t *>(lds + L.list);
+  int32_t *s_off = reinterpret_cast<int32_t *>(lds + L.off);
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int col = lane & 31, h = lane >> 5;
   const int NG = nobj * npoint;              // groups of this workgroup
 
-  tile_copy_async<WAVES>(wpack, s_w0, RESIDENT ? TOTAL : T1, wave, lane);
-  {
-    const float *gx = xyz + (size_t)obj0 * n * 3;
-    const float *gc = new_xyz + (size_t)obj0 * npoint * 3;
-    const int32_t *gi = idx + (size_t)obj0 * npoint * kNS;
-    if (PM) {
-      const float *gf = feats + (size_t)obj0 * n * ld_feat;
-      for (int e = tid; e < nobj * CF * n; e += BLOCK) {
-        const int pp = e / CF, c = e - pp * CF;                 // pp = o * n + p
-        const int o = OBJS > 1 ? pp / n : 0;
-        s_feat[o * CF * n + c * n + (pp - o * n)] = gf[(size_t)pp * ld_feat + c];
-      }
-    } else {
-      const float *gf = feats + (size_t)obj0 * CF * n;
-      if (((CF * n) & 3) == 0) {
-        const float4 *g4 = reinterpret_cast<const float4 *>(gf);
-        float4 *l4 = reinterpret_cast<float4 *>(s_feat);
-        for (int e = tid; e < (nobj * CF * n) >> 2; e += BLOCK) l4[e] = g4[e];
-      } else {
-        for (int e = tid; e < nobj * CF * n; e += BLOCK) s_feat[e] = gf[e];
-      }
-    }
-    for (int e = tid; e < nobj * n * 3; e += BLOCK) s_xyz[e] = gx[e];
-    for (int e = tid; e < NG * 3; e += BLOCK) s_ctr[e] = gc[e];
-    for (int e = tid; e < NG * kNS; e += BLOCK) s_idx[e] = gi[e];
-    for (int e = tid; e < NG * OLD; e += BLOCK) s_out[e] = 0;
-  }
+  const WeightStream<GEO, WAVES, RESIDENT> ws{wpack, lds, wave, lane};
+  ws.first();
+  stage_objects<CF, PM, OBJS, BLOCK>(obj0, nobj, n, npoint, xyz, new_xyz, feats, idx, ld_feat, s_feat, s_xyz, s_ctr, s_idx, tid);
+  for (int e = tid; e < NG * OLD; e += BLOCK) s_out[e] = 0;
   __syncthreads();
 
   // ---- the kept columns: slot c > 0 of a group is dropped iff idx[c] == idx[0] -----------------------------------
@@ -764,28 +759,6 @@ __global__ __launch_bounds__(WAVES * 64) void sa_mlp_x3_distinct_kernel(
   tile_copy_wait();
   __syncthreads();
 
-  auto tile_off = [&](int g, int &len) -> int {      // offset (floats) of weight tile g (mod G)
-    if (g >= G) g -= G;
-    if (g < M1) { len = T1; return g * T1; }
-    if (g < M1 + M2) { len = T2; return M1 * T1 + (g - M1) * T2; }
-    len = T3;
-    return M1 * T1 + M2 * T2 + (g - M1 - M2) * T3;
-  };
-  auto stage_begin = [&](int rd, int g) -> const float * {
-    int len;
-    if (RESIDENT) return s_w0 + tile_off(g, len);
-    const int gg = rd * G + g;
-    const int off = tile_off(g + 1, len);
-    tile_copy_async<WAVES>(wpack + off, (gg & 1) ? s_w0 : s_w1, len, wave, lane);
-    return (gg & 1) ? s_w1 : s_w0;
-  };
-  auto stage_end = [&]() {
-    if (!RESIDENT) {
-      tile_copy_wait();
-      __syncthreads();
-    }
-  };
-
   const int total = __builtin_amdgcn_readfirstlane(s_off[NG]);   // >= NG: slot 0 of a group is always kept
   const int ntiles = (total + 31) >> 5;
   const int rounds = (ntiles + WAVES - 1) / WAVES;
@@ -793,17 +766,16 @@ __global__ __launch_bounds__(WAVES * 64) void sa_mlp_x3_distinct_kernel(
     const int tile = rd * WAVES + wave;
     if (tile >= ntiles) {                    // wave-uniform: a wave without a tile only keeps the weight stream going
       if (RESIDENT) break;
-      for (int g = 0; g < G; ++g) {          // the same copies and barriers as the waves that compute
-        stage_begin(rd, g);
-        stage_end();
+      for (int g = 0; g < GEO::G; ++g) {     // the same copies and barriers as the waves that compute
+        ws.begin(rd, g);
+        ws.end();
       }
       continue;
     }
 
-    bf16x8 a0h[S1], a0l[S1];
+    bf16x8 a0h[GEO::S1], a0l[GEO::S1];
     // pooled layer: accumulator register r of this lane holds column cbase + (r & 3) + 8 * (r >> 2) of the list
     unsigned int cut = 0;                    // bit r: that column may be of another group than register r - 1's (or is past the end)
-    const int cbase = tile * kNS + 4 * h;
     int rkey[16];                            // group of register r's column, -1 past the end of the list
     int g_first;                             // group of the tile's first column
     bool uni;                                // the tile is 32 columns of ONE group: pooled like a dense tile
@@ -812,27 +784,7 @@ __global__ __launch_bounds__(WAVES * 64) void sa_mlp_x3_distinct_kernel(
       const int ent = s_list[ei];
       const int j = ent >> 16, p = ent & 0xFFFF;                 // j = o * npoint + group of the object
       const int o = OBJS > 1 ? j / npoint : 0;
-      const float *fo = s_feat + o * CF * n + p;
-      const float *xo = s_xyz + (o * n + p) * 3;
-      const float *co = s_ctr + j * 3;
-#pragma unroll
-      for (int s = 0; s < S1; ++s) {
-        f32x8 v;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const int k = slot_channel16(s, e, h);
-          float x;
-          if (slot_channel16(s, e, 0) >= 3 && slot_channel16(s, e, 1) < CIN) {
-            x = fo[(k - 3) * n];
-          } else {
-            x = 0.f;
-            if (k < 3) x = xo[k] - co[k];
-            else if (k < CIN) x = fo[(k - 3) * n];
-          }
-          v[e] = x;
-        }
-        split8(v, a0h[s], a0l[s]);
-      }
+      gather_layer1<GEO>(s_feat + o * CF * n + p, n, s_xyz + (o * n + p) * 3, s_ctr + j * 3, h, a0h, a0l);
       // where the group changes along the tile: one ballot over the columns (= lanes), no LDS traffic
       const int key = tile * kNS + col < total ? j : -1;
       const int left = __shfl_up(key, 1, 64);
@@ -853,24 +805,10 @@ __global__ __launch_bounds__(WAVES * 64) void sa_mlp_x3_distinct_kernel(
         if (m) cut |= 1u << r;
       }
     }
-    bf16x8 a1h[S2], a1l[S2], a2h[S3], a2l[S3];
-    auto split_tile = [&](const f32x16 &acc, bf16x8 &h0, bf16x8 &l0, bf16x8 &h1, bf16x8 &l1) {
-      f32x8 v0, v1;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) { v0[e] = relu1(acc[e]); v1[e] = relu1(acc[8 + e]); }
-      split8(v0, h0, l0);
-      split8(v1, h1, l1);
-    };
-    // transposed last layer: lane = output channel, registers (+ the other half of the wave) = the 32 columns
-    auto pool_tile = [&](const f32x16 &acc, int mt) {
+    mlp_tile<GEO, NPROD>(ws, rd, a0h, a0l, lane, [=](const f32x16 &acc, int mt) {
       int *row = s_out + mt * 32 + col;
       if (uni) {
-        float m0 = fmaxf(fmaxf(acc[0], acc[1]), fmaxf(acc[2], acc[3]));
-        float m1 = fmaxf(fmaxf(acc[4], acc[5]), fmaxf(acc[6], acc[7]));
-        float m2 = fmaxf(fmaxf(acc[8], acc[9]), fmaxf(acc[10], acc[11]));
-        float m3 = fmaxf(fmaxf(acc[12], acc[13]), fmaxf(acc[14], acc[15]));
-        float m = fmaxf(fmaxf(m0, m1), fmaxf(m2, m3));
-        m = fmaxf(m, __shfl_xor(m, 32, 64));
+        const float m = group_max(acc);
         if (lane < 32) atomicMax(row + g_first * OLD, __float_as_int(m));
         return;
       }
@@ -888,36 +826,7 @@ __global__ __launch_bounds__(WAVES * 64) void sa_mlp_x3_distinct_kernel(
         }
       }
       fold(15, m);
-    };
-    int g = 0;
-    f32x16 prev;
-#pragma unroll
-    for (int mt = 0; mt < M1; ++mt, ++g) {
-      const float *wt = stage_begin(rd, g);
-      const f32x16 acc = mfma_tile16<S1, false, NPROD>(wt, a0h, a0l, lane);
-      if (mt > 0) split_tile(prev, a1h[2 * mt - 2], a1l[2 * mt - 2], a1h[2 * mt - 1], a1l[2 * mt - 1]);
-      prev = acc;
-      stage_end();
-    }
-    split_tile(prev, a1h[2 * M1 - 2], a1l[2 * M1 - 2], a1h[2 * M1 - 1], a1l[2 * M1 - 1]);
-#pragma unroll
-    for (int mt = 0; mt < M2; ++mt, ++g) {
-      const float *wt = stage_begin(rd, g);
-      const f32x16 acc = mfma_tile16<S2, false, NPROD>(wt, a1h, a1l, lane);
-      if (mt > 0) split_tile(prev, a2h[2 * mt - 2], a2l[2 * mt - 2], a2h[2 * mt - 1], a2l[2 * mt - 1]);
-      prev = acc;
-      stage_end();
-    }
-    split_tile(prev, a2h[2 * M2 - 2], a2l[2 * M2 - 2], a2h[2 * M2 - 1], a2l[2 * M2 - 1]);
-#pragma unroll
-    for (int mt = 0; mt < M3; ++mt, ++g) {
-      const float *wt = stage_begin(rd, g);
-      const f32x16 acc = mfma_tile16<S3, true, NPROD>(wt, a2h, a2l, lane);
-      if (mt > 0) pool_tile(prev, mt - 1);
-      prev = acc;
-      stage_end();
-    }
-    pool_tile(prev, M3 - 1);
+    });
   }
   __syncthreads();
   // ---- pooled rows out: (object, channel, group) in HBM, [group][channel] here ----------------------------------
@@ -941,18 +850,6 @@ __global__ __launch_bounds__(WAVES * 64) void sa_mlp_x3_distinct_kernel(
   }
 }
 
-template <int CF, int C1, int C2, int C3, int OBJS, bool RESIDENT>
-size_t distinct_lds_bytes(int n, int npoint) {
-  constexpr int CIN = 3 + CF;
-  constexpr int T1 = tile_floats16(CIN), T2 = tile_floats16(C1), T3 = tile_floats16(C2);
-  constexpr int TMAX = T1 > T2 ? (T1 > T3 ? T1 : T3) : (T2 > T3 ? T2 : T3);
-  constexpr int TOTAL = (C1 / 32) * T1 + (C2 / 32) * T2 + (C3 / 32) * T3;
-  constexpr int WBUF = RESIDENT ? TOTAL : 2 * TMAX;
-  const size_t o = OBJS;
-  return sizeof(float) * ((size_t)WBUF + ((o * npoint * (C3 + 1) + 3) & ~(size_t)3) + o * CF * n + o * n * 3 +
-                          o * npoint * 3 + 2 * o * npoint * kNS + o * npoint + 1);
-}
-
 static int g_products = 3;      // 3 = split-bf16 triple product (fp32-accurate, default); 1 = single bf16 product (opt-in)
 // 0 = every launch runs the MLP on all 32 slots; 1 (default) = the streamed-weight form (SA2) runs it on each group's distinct
 // samples only; 2 = so does the resident-weight form (SA1), where it measured slower than the dense kernel
@@ -961,14 +858,24 @@ static int g_distinct = 1;
 
 template <int CF, int C1, int C2, int C3, int WAVES, bool RESIDENT, bool PM, int NPROD>
 int launch_sa_x3_n(int b, int n, int npoint, const float *xyz, const float *new_xyz, const float *feats,
-                   const int32_t *idx, const float *wpack, float *out, hipStream_t s, int ld_feat);
+                   const int32_t *idx, const float *wpack, float *out, hipStream_t s, int ld_feat) {
+  const size_t lds = Layout<Geometry16<CF, C1, C2, C3>, RESIDENT, 1, false, size_t>(n, npoint).bytes();
+  if (lds > 160 * 1024) return GPS_ERR_UNSUPPORTED;
+  static gps_dev::PerDevice<size_t, 1> granted;
+  const int st = gps_dev::grant_lds(reinterpret_cast<const void *>(&sa_mlp_x3_kernel<CF, C1, C2, C3, WAVES, RESIDENT, PM, NPROD>),
+                                    lds, lds, granted.row()[0]);
+  if (st != GPS_OK) return st;
+  hipLaunchKernelGGL((sa_mlp_x3_kernel<CF, C1, C2, C3, WAVES, RESIDENT, PM, NPROD>), dim3(b), dim3(WAVES * 64), lds, s, b, n,
+                     npoint, xyz, new_xyz, feats, idx, wpack, out, ld_feat, gps::object_extent());
+  return GPS_OK;
+}
 
 // OBJS objects per workgroup when LDS admits them, else fewer; shapes the distinct form cannot hold (its column list and
 // pooled-row pitch need more LDS than the dense form; point / group ids are packed in 16 + 15 bits) run the dense kernel
 template <int CF, int C1, int C2, int C3, int WAVES, bool RESIDENT, bool PM, int NPROD, int OBJS>
 int launch_sa_x3_distinct(int b, int n, int npoint, const float *xyz, const float *new_xyz, const float *feats,
                           const int32_t *idx, const float *wpack, float *out, hipStream_t s, int ld_feat) {
-  const size_t lds = distinct_lds_bytes<CF, C1, C2, C3, OBJS, RESIDENT>(n, npoint);
+  const size_t lds = Layout<Geometry16<CF, C1, C2, C3>, RESIDENT, OBJS, true, size_t>(n, npoint).bytes();
   if (lds > 160 * 1024 || n > 0xFFFF || (long long)OBJS * npoint > 0x7FFF) {
     if constexpr (OBJS > 1)
       return launch_sa_x3_distinct<CF, C1, C2, C3, WAVES, RESIDENT, PM, NPROD, OBJS - 1>(b, n, npoint, xyz, new_xyz, feats, idx,
@@ -976,13 +883,10 @@ int launch_sa_x3_distinct(int b, int n, int npoint, const float *xyz, const floa
     else
       return launch_sa_x3_n<CF, C1, C2, C3, WAVES, RESIDENT, PM, NPROD>(b, n, npoint, xyz, new_xyz, feats, idx, wpack, out, s, ld_feat);
   }
-  static size_t attr_lds = 0;
-  if (lds > attr_lds) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(&sa_mlp_x3_distinct_kernel<CF, C1, C2, C3, WAVES, RESIDENT, PM, NPROD, OBJS>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return GPS_ERR_LAUNCH;
-    attr_lds = lds;
-  }
+  static gps_dev::PerDevice<size_t, 1> granted;
+  const int st = gps_dev::grant_lds(reinterpret_cast<const void *>(&sa_mlp_x3_distinct_kernel<CF, C1, C2, C3, WAVES, RESIDENT, PM, NPROD, OBJS>),
+                                    lds, lds, granted.row()[0]);
+  if (st != GPS_OK) return st;
   hipLaunchKernelGGL((sa_mlp_x3_distinct_kernel<CF, C1, C2, C3, WAVES, RESIDENT, PM, NPROD, OBJS>), dim3((b + OBJS - 1) / OBJS),
                      dim3(WAVES * 64), lds, s, b, n, npoint, xyz, new_xyz, feats, idx, wpack, out, ld_feat, gps::object_extent());
   return GPS_OK;
@@ -1002,50 +906,26 @@ int launch_sa_x3(int b, int n, int npoint, const float *xyz, const float *new_xy
              : launch_sa_x3_n<CF, C1, C2, C3, WAVES, RESIDENT, PM, 3>(b, n, npoint, xyz, new_xyz, feats, idx, wpack, out, s, ld_feat);
 }
 
-template <int CF, int C1, int C2, int C3, int WAVES, bool RESIDENT, bool PM, int NPROD>
-int launch_sa_x3_n(int b, int n, int npoint, const float *xyz, const float *new_xyz, const float *feats,
-                   const int32_t *idx, const float *wpack, float *out, hipStream_t s, int ld_feat) {
-  constexpr int CIN = 3 + CF;
-  constexpr int T1 = tile_floats16(CIN), T2 = tile_floats16(C1), T3 = tile_floats16(C2);
-  constexpr int TMAX = T1 > T2 ? (T1 > T3 ? T1 : T3) : (T2 > T3 ? T2 : T3);
-  constexpr int TOTAL = (C1 / 32) * T1 + (C2 / 32) * T2 + (C3 / 32) * T3;
-  constexpr int WBUF = RESIDENT ? TOTAL : 2 * TMAX;
-  const size_t lds = sizeof(float) * ((size_t)WBUF + (size_t)C3 * npoint + (size_t)CF * n + (size_t)n * 3 +
-                                      (size_t)npoint * 3 + (size_t)npoint * kNS);
-  if (lds > 160 * 1024) return GPS_ERR_UNSUPPORTED;
-  static size_t attr_lds = 0;
-  if (lds > attr_lds) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(&sa_mlp_x3_kernel<CF, C1, C2, C3, WAVES, RESIDENT, PM, NPROD>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return GPS_ERR_LAUNCH;
-    attr_lds = lds;
-  }
-  hipLaunchKernelGGL((sa_mlp_x3_kernel<CF, C1, C2, C3, WAVES, RESIDENT, PM, NPROD>), dim3(b), dim3(WAVES * 64), lds, s, b, n,
-                     npoint, xyz, new_xyz, feats, idx, wpack, out, ld_feat, gps::object_extent());
-  return GPS_OK;
-}
-
 }  // namespace x3
 
 }  // namespace gps_sa
 
 extern "C" {
 
-long long gps_sa_mlp_wpack_floats(int c_in, int c1, int c2, int c3) {
-  if (c_in < 1 || c1 < 32 || c2 < 32 || c3 < 32 || (c1 & 31) || (c2 & 31) || (c3 & 31)) return -1;
-  return (long long)(c1 / 32) * gps_sa::tile_floats(c_in) + (long long)(c2 / 32) * gps_sa::tile_floats(c1) +
-         (long long)(c3 / 32) * gps_sa::tile_floats(c2);
-}
-
 long long gps_sa_mlp_layer_floats(int c_in, int c_out) {
   if (c_in < 1 || c_out < 32 || (c_out & 31)) return -1;
   return (long long)(c_out / 32) * gps_sa::tile_floats(c_in);
 }
 
+long long gps_sa_mlp_wpack_floats(int c_in, int c1, int c2, int c3) {
+  if (c_in < 1 || c1 < 32 || c2 < 32 || c3 < 32 || (c1 & 31) || (c2 & 31) || (c3 & 31)) return -1;
+  return gps_sa_mlp_layer_floats(c_in, c1) + gps_sa_mlp_layer_floats(c1, c2) + gps_sa_mlp_layer_floats(c2, c3);
+}
+
 int gps_sa_mlp_pack_layer(int c_in, int c_out, const float *w, const float *shift, float *dst,
                           gps_stream_t stream) {
   if (c_in < 1 || c_out < 32 || (c_out & 31) || !w || !shift || !dst) return GPS_ERR_INVALID_ARGUMENT;
-  const int total = (c_out / 32) * gps_sa::tile_floats(c_in);
+  const int total = (int)gps_sa_mlp_layer_floats(c_in, c_out);
   hipLaunchKernelGGL(gps_sa::pack_layer_kernel, dim3((total + 255) / 256), dim3(256), 0,
                      (hipStream_t)stream, c_in, c_out, w, shift, dst);
   return hipGetLastError() == hipSuccess ? GPS_OK : GPS_ERR_LAUNCH;
@@ -1071,7 +951,7 @@ long long gps_sa_mlp_layer_floats_bf16x3(int c_in, int c_out) {
 int gps_sa_mlp_pack_layer_bf16x3(int c_in, int c_out, const float *w, const float *shift, float *dst,
                                  gps_stream_t stream) {
   if (c_in < 1 || c_out < 32 || (c_out & 31) || !w || !shift || !dst) return GPS_ERR_INVALID_ARGUMENT;
-  const int total = (c_out / 32) * gps_sa::x3::tile_floats16(c_in);
+  const int total = (int)gps_sa_mlp_layer_floats_bf16x3(c_in, c_out);
   hipLaunchKernelGGL(gps_sa::x3::pack_layer16_kernel, dim3((total + 255) / 256), dim3(256), 0,
                      (hipStream_t)stream, c_in, c_out, w, shift, dst);
   return hipGetLastError() == hipSuccess ? GPS_OK : GPS_ERR_LAUNCH;

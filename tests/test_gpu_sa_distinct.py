@@ -7,10 +7,16 @@ gps_ball_query.  max over a set = max over the set with repeats, so the two form
 
 Tolerances: 1e-4 * max|ref| against fp64 for the split-bf16 triple product (tests/test_gpu_sa_fused.py); for the
 single-product mode the tolerance stated there, max|diff| <= 2e-2 * max|ref| and relative L2 <= 1e-2."""
+import os
+import sys
+
 import pytest
 import torch
 
 from sceneverse_amd.pointnet2 import _ext
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+import sa_mlp_digests  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -94,19 +100,28 @@ def _reference(xyz, new_xyz, feats, idx, ws, shifts):
     return x.max(dim=3).values
 
 
-@pytest.fixture(scope="module")
-def cases():
-    """inputs, packed weights and the fp64 reference of every (level, pattern): computed once, never modified."""
+def _level_inputs(level):
+    return _inputs(level, 7 + list(SHAPES).index(level))
+
+
+def _build_cases():
+    """inputs, packed weights and the fp64 reference of every (level, pattern)."""
     out = {}
     for li, level in enumerate(SHAPES):
         b, n, npoint, c, ch = SHAPES[level]
-        xyz, new_xyz, feats, ws, shifts = _inputs(level, 7 + li)
+        xyz, new_xyz, feats, ws, shifts = _level_inputs(level)
         dev = [t.to(DEV) for t in (xyz, new_xyz, feats)]
         wpack = _ext.sa_mlp_pack([w.to(DEV) for w in ws], [s.to(DEV) for s in shifts], "bf16x3")
         for pi, pattern in enumerate(PATTERNS):
             idx = _idx(pattern, b, n, npoint, 100 * li + pi)
             out[level, pattern] = (dev, idx.to(DEV), wpack, ch, _reference(xyz, new_xyz, feats, idx, ws, shifts).float())
     return out
+
+
+@pytest.fixture(scope="module")
+def cases():
+    """computed once, never modified"""
+    return _build_cases()
 
 
 def _run(level, case, entry, extent):
@@ -228,3 +243,41 @@ def test_shape_too_large_for_the_column_list_runs_the_dense_kernel():
     assert torch.equal(got.view(torch.int32), dense.view(torch.int32))
     ref = _reference(xyz.cpu(), new_xyz.cpu(), feats.cpu(), idx.cpu(), [w.cpu() for w in ws], [s.cpu() for s in shifts]).float()
     assert (got.cpu() - ref).abs().max().item() <= 1e-4 * ref.abs().max().item()
+
+
+def test_frozen_digests_cover_every_case():
+    assert sa_mlp_digests.PATTERNS == PATTERNS
+    assert sorted(sa_mlp_digests.load()) == sorted(sa_mlp_digests.keys())
+
+
+@pytest.mark.parametrize("key", sa_mlp_digests.keys())
+def test_output_bits_are_the_frozen_ones(cases, key):
+    """tests/golden/sa_mlp_digests.json (tools/sa_mlp_digests.py): SHA-256 of the raw output, sentinel rows included, of the
+    dense and the distinct bf16x3 kernels on every case above and of the fp32 kernel on four of them.  Both forms are
+    deterministic -- fixed MFMA order, order-independent integer max -- so a mismatch is a change of arithmetic to explain
+    (a term moved across the split8 subtraction, another accumulator initialisation), never a tolerance."""
+    assert sa_mlp_digests.compute(key, cases, sys.modules[__name__]) == sa_mlp_digests.load()[key]
+
+
+@pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two GPUs")
+def test_second_device_of_the_process_gets_its_own_lds_grant():
+    """SA1 form with n = 1024, npoint = 32: 104 KB of dynamic LDS, above the 64 KiB a kernel has without opting in.  The
+    opt-in belongs to the (kernel, device) pair: the launch on cuda:1 after one on cuda:0 must be granted too."""
+    b, n, npoint, c, ch = 2, 1024, 32, 3, (64, 64, 128)
+    g = torch.Generator().manual_seed(11)
+    xyz = torch.rand(b, n, 3, generator=g) * 2 - 1
+    new_xyz = torch.rand(b, npoint, 3, generator=g) * 2 - 1
+    feats = torch.randn(b, c, n, generator=g)
+    idx = torch.randint(0, n, (b, npoint, 32), generator=g, dtype=torch.int32)
+    ws, shifts, c_in = [], [], 3 + c
+    for c_out in ch:
+        ws.append(torch.randn(c_out, c_in, generator=g) / c_in ** 0.5)
+        shifts.append(torch.randn(c_out, generator=g) * 0.1)
+        c_in = c_out
+    outs = []
+    for d in ("cuda:0", "cuda:1"):
+        wpack = _ext.sa_mlp_pack([w.to(d) for w in ws], [s.to(d) for s in shifts], "bf16x3")
+        out = _ext.sa_mlp_forward(xyz.to(d), new_xyz.to(d), feats.to(d), idx.to(d), wpack, ch, "bf16x3")
+        torch.cuda.synchronize(d)
+        outs.append(out.cpu())
+    assert torch.equal(outs[0], outs[1])
