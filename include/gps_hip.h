@@ -682,6 +682,59 @@ GPS_API int gps_refer_metrics(int B, int O, const void *og3d_logits, long long l
                               const int64_t *iou25, const int64_t *iou50, const int64_t *tgt_id,
                               const uint8_t *is_multiple, int64_t *counters, gps_stream_t stream);
 
+/* ---- accuracy counters of the pre-train, ReferIt3D and object-class evaluators -------------------------
+ * Replaces the arg-max / compare / sum / `.item()` chains of PretrainEval.batch_metrics (evaluator/pretrain_eval.py:21-67),
+ * ReferIt3DEval.batch_metrics (evaluator/referit3d_eval.py:14-83) and PretrainObjEval.batch_metrics
+ * (evaluator/objcls_eval.py:14-23), and the float bookkeeping of PretrainEval.update / record (:69-86).
+ *
+ * gps_cls_hits: up to GPS_CLS_HITS_MAX_PROBLEMS problems (GPS_ERR_UNSUPPORTED above), passed by value into ONE launch.
+ *   Per problem: logits (rows, ld >= cols) f32 or (logits_bf16 != 0) bf16, element-aligned, rows at ANY element
+ *   alignment; labels (rows) int64; rows_dev: optional device int32, rows at or past *rows_dev are dead (not read, not
+ *   counted); sel / split_a / split_b: optional per-row masks of mask_elem_bytes (1: bool / uint8, 8: int64) bytes per
+ *   row, nonzero = true, sel NULL = every row; counters: 6 int64 words.
+ *   A live row is COUNTED iff sel is true and (use_ignore == 0 or label != ignore_index).  A counted row is a HIT iff
+ *   argmax(logits[row, :cols]) == label under torch.argmax's rule: NaN is the greatest value, the first index among
+ *   equals wins, a row of -inf gives 0.  A label outside [0, cols) never hits.  The launch ADDS
+ *     counters[0] += hits   [1] += counted   [2] += hits & a   [3] += counted & a   [4] += hits & b   [5] += counted & b
+ *   (a NULL split counts as all-false).  Rows that are not counted are not read; columns [cols, ld) are never read; no
+ *   load leaves the rows x ld elements of the problem.  Rows of cols <= GPS_CLS_HITS_WAVE_MAX_COLS take one wave each,
+ *   wider rows one 256-thread workgroup each; both read 16-byte granules between a scalar head and a scalar tail.  Integer atomics
+ *   only: the counts do not depend on order or on the run.  The caller (or gps_metrics_fold) zeroes the counters.
+ *   Checked before any launch: negative rows, cols <= 0, ld < cols, mask_elem_bytes not 1 / 8, a missing or misaligned
+ *   logits / labels / counters pointer of a problem with rows > 0: GPS_ERR_INVALID_ARGUMENT.  n_problems == 0 or every
+ *   rows == 0: GPS_OK, nothing launched.
+ *
+ * gps_metrics_fold: one tiny launch that turns a batch's counts into the reference's float64 bookkeeping, one rounding
+ *   per operation.  n_terms <= GPS_METRICS_MAX_TERMS terms (host array, passed by value).  Per term k:
+ *     h = *hits - (sub_hits ? *sub_hits : 0),  c = *count - (sub_count ? *sub_count : 0)
+ *     last[k] = (double)h / (use_const_denominator ? const_denominator : (double)c + eps);   acc[k] += last[k] * weight
+ *   With n_mean > 0, slot n_terms is the mean of the first n_mean ratios (added left to right from 0.0, divided by
+ *   n_mean) with the same last / acc treatment.  Then total[0] += weight and every counter word the terms name is set
+ *   back to zero.  last, acc: n_terms + 1 doubles; total: 1 double.  count may be NULL with a constant denominator. */
+#define GPS_CLS_HITS_MAX_PROBLEMS 8
+#define GPS_CLS_HITS_WAVE_MAX_COLS 1024
+#define GPS_METRICS_MAX_TERMS 16
+typedef struct gps_cls_hits_problem {
+  int rows, cols;
+  const void *logits;
+  long long ld;
+  int logits_bf16, use_ignore;
+  long long ignore_index;
+  const int64_t *labels;
+  const int32_t *rows_dev;
+  const void *sel, *split_a, *split_b;
+  int mask_elem_bytes, reserved;
+  int64_t *counters;
+} gps_cls_hits_problem;
+typedef struct gps_metric_term {
+  int64_t *hits, *count, *sub_hits, *sub_count;
+  double eps, const_denominator;
+  int use_const_denominator, reserved;
+} gps_metric_term;
+GPS_API int gps_cls_hits(const gps_cls_hits_problem *problems, int n_problems, gps_stream_t stream);
+GPS_API int gps_metrics_fold(int n_terms, const gps_metric_term *terms, double weight, int n_mean, double *last,
+                             double *acc, double *total, gps_stream_t stream);
+
 /* ---- bias gradients: column sums of a bf16 matrix ---------------------------------------------------
  * Replaces the `dY.sum(0)` autograd derives for the bias of every nn.Linear in the transformer stacks
  * (modules/layers/transformers.py:115-154, 285-316; HF BertLayer behind modules/language/bert.py:21-26).

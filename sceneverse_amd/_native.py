@@ -68,6 +68,21 @@ class AttnArgs(ctypes.Structure):
                 ("delta_ws", _vp)]
 
 
+class ClsHitsProblem(ctypes.Structure):
+    """struct gps_cls_hits_problem of include/gps_hip.h, field for field."""
+    _fields_ = [("rows", _i), ("cols", _i), ("logits", _vp), ("ld", ctypes.c_longlong), ("logits_bf16", _i),
+                ("use_ignore", _i), ("ignore_index", ctypes.c_longlong), ("labels", _vp), ("rows_dev", _vp),
+                ("sel", _vp), ("split_a", _vp), ("split_b", _vp), ("mask_elem_bytes", _i), ("reserved", _i),
+                ("counters", _vp)]
+
+
+class MetricTerm(ctypes.Structure):
+    """struct gps_metric_term of include/gps_hip.h, field for field."""
+    _fields_ = [("hits", _vp), ("count", _vp), ("sub_hits", _vp), ("sub_count", _vp), ("eps", ctypes.c_double),
+                ("const_denominator", ctypes.c_double), ("use_const_denominator", _i), ("reserved", _i)]
+
+
+CLS_HITS_MAX_PROBLEMS, CLS_HITS_WAVE_MAX_COLS, METRICS_MAX_TERMS = 8, 1024, 16
 ATTN_BF16, ATTN_F32 = 0, 1
 ATTN_COMPUTE_NATIVE, ATTN_COMPUTE_FP8 = 0, 1
 GEMM_NT, GEMM_NN, GEMM_TN = 0, 1, 2
@@ -116,6 +131,8 @@ SIGNATURES = {
     "gps_obj_boxes": [_i, ctypes.c_longlong, _i, _vp, _i, _vp, _vp, _vp, _vp],
     "gps_refer_targets": [_i, _i, _i, _i] + [_vp] * 10,
     "gps_refer_metrics": [_i, _i, _vp, ctypes.c_longlong, _i] + [_vp] * 6,
+    "gps_cls_hits": [ctypes.POINTER(ClsHitsProblem), _i, _vp],
+    "gps_metrics_fold": [_i, ctypes.POINTER(MetricTerm), ctypes.c_double, _i, _vp, _vp, _vp, _vp],
     "gps_embedding_grad_scratch_ints": [_i, _i, _i],
     "gps_embedding_grad": [_i, _i, _i, _vp, _vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, _vp],
     "gps_loc_embed_partial_rows": [_i],

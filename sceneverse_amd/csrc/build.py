@@ -26,6 +26,7 @@ SOURCES = [
     ("gps_layernorm.hip", []),
     ("gps_objects.hip", []),
     ("gps_refer.hip", ["-ffp-contract=off"]),
+    ("gps_metrics.hip", ["-ffp-contract=off"]),
     ("gps_reduce.hip", []),
     ("gps_embedding.hip", []),
     ("gps_bert_embed.hip", []),

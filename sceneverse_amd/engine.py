@@ -63,7 +63,7 @@ class GPSTrainStep:
                  bucket_cap_mb: int = 64, seed: int = 42, graph: bool = False, graph_warmup: int = 3,
                  native_gemm: bool = True, grad_compress: Optional[str] = None, native_optimizer: bool = True,
                  fused_lm_loss: bool = True, find_unused_parameters: bool = False, wgrad_overlap: bool = False,
-                 wgrad_group: bool = True):
+                 wgrad_group: bool = True, train_metrics=False):
         self.cfg = cfg
         self.device = torch.device(device)
         # projections / FFNs of the transformer stacks on libgps_hip.so's MFMA GEMMs (modules/layers/gemm.py);
@@ -162,6 +162,14 @@ class GPSTrainStep:
         self._exchange_events = None          # (start, end) events around the EXPOSED part of the gradient exchange
         # tests / diagnostics: called with a stage name at the capture / replay points of the split-graph step
         self.stage_hook = None
+        # train_metrics: False (default: the step's launches, outputs and graphs are untouched), True, or the names of the
+        # PretrainCounter keys to compute.  The reference's trainer calls evaluator["train"].batch_metrics on every
+        # training step (trainer/default_trainer.py); here the counts stay on the device: the update is issued behind
+        # the losses, inside whatever graph holds them, and `train_metrics()` hands out the last step's ratios.
+        self.metric_counter = None
+        self.metrics_hook = None              # tests: called as hook(engine, out) right before the counter's update
+        if train_metrics is not False and train_metrics is not None:
+            self.metric_counter = PretrainCounter(self.device, keys=None if train_metrics is True else train_metrics)
         if self.graph_dp and dist_utils.is_dist():
             with torch.no_grad():                      # what DDP does at construction
                 for t in list(self.model.parameters()) + list(self.model.buffers()):
@@ -315,8 +323,9 @@ class GPSTrainStep:
                 with self._autocast():
                     out = self.net(data_dict)
                 self._gather_features(out)
-                with self._autocast():
+                with self._autocast(), self._metrics_sink():
                     total, losses = self.loss(out)
+                self._update_metrics(out)
                 self.optimizer.zero_grad(set_to_none=True)
                 self._backward(total)
                 grads = [p.grad for p in self.model.parameters() if p.grad is not None]
@@ -401,8 +410,9 @@ class GPSTrainStep:
                 for lo, hi in zero_ranges:
                     self._flat_grad[lo:hi].zero_()
                 _gemm.mark_stale_grads(direct_params)
-                with self._autocast():
+                with self._autocast(), self._metrics_sink():
                     total, losses = self.loss(out)
+                self._update_metrics(out)
                 if segmented and not _cut_is_valid(total, boundary, bottom):
                     # a gradient path from the loss into a bottom-segment parameter that does not cross a boundary
                     # tensor (a head reading an encoder-internal tensor, a tied weight ...): the staged backward would
@@ -605,11 +615,36 @@ class GPSTrainStep:
         self._begin_step()
         with self._autocast():
             out = self.net(data_dict)
-            total, losses = self.loss(out)
+            with self._metrics_sink():
+                total, losses = self.loss(out)
         return out, total, losses
+
+    def _metrics_sink(self):
+        """Around a loss evaluation: the fused masked-LM loss adds its hit count to the metric counter's words."""
+        c = self.metric_counter
+        if c is None or not self.net.training or not c._wanted("lang_cls_acc_mask"):
+            return contextlib.nullcontext()
+        return c.sink()
+
+    def _update_metrics(self, out) -> None:
+        """The per-step `batch_metrics` of the reference's trainer: two launches behind the losses, no host sync."""
+        if self.metric_counter is None:
+            return
+        if self.metrics_hook is not None:
+            self.metrics_hook(self, out)
+        with torch.no_grad():
+            self.metric_counter.update(out)
+
+    def train_metrics(self) -> dict:
+        """The last step's pre-train accuracies ({key: 0-dim float64 device tensor}; no host sync); needs
+        `train_metrics=` at construction.  `metric_counter.result()` gives the running averages."""
+        if self.metric_counter is None:
+            raise RuntimeError("GPSTrainStep was built without train_metrics")
+        return self.metric_counter.last()
 
     def _eager_body(self, data_dict):
         out, total, losses = self.forward_loss(data_dict)
+        self._update_metrics(out)
         self.optimizer.zero_grad(set_to_none=True)
         self._backward(total)
         self._clip_and_step()
@@ -702,6 +737,7 @@ class GPSTrainStep:
             ctx = torch.cuda.stream(self._stream())
         with ctx:
             out, total, losses = self.forward_loss(data_dict)
+            self._update_metrics(out)
             self.optimizer.zero_grad(set_to_none=True)
             self._backward(total)
             self._clip_and_step()
@@ -812,6 +848,238 @@ class ScanReferCounter:
         if include_count:
             return pairs
         return {k: h / max(n, 1) for k, (h, n) in pairs.items()}
+
+
+def _need_gpu(name: str, *tensors) -> None:
+    for t in tensors:
+        if torch.is_tensor(t) and t.device.type != "cuda":
+            raise RuntimeError(f"{name} runs on libgps_hip.so: its tensors and counters must live on a GPU (no CPU path)")
+
+
+class PretrainCounter:
+    """PretrainEval (evaluator/pretrain_eval.py:21-86) with counts and bookkeeping that stay on the device:
+    `batch_metrics`, `update` and `record` restated.  One `update` is ONE gps_cls_hits launch over all its arg-max
+    problems plus one gps_metrics_fold launch -- no `.item()`, so a training step can issue it every iteration and a
+    captured step replays it.  `last()` hands out the last batch's ratios as 0-dim float64 device tensors (clones, no
+    sync: what a trainer logs per step); `result()` is the one read-back: per key sum(ratio * B) / sum(B).
+
+    Keys, present exactly when the reference computes them (its insertion order, which `target_metric` averages in):
+    og_acc (needs `tgt_object_id`, and `og3d_logits`, without which the reference raises; / float(B)), lang_cls_acc_mask, obj_cls_post_acc / _unmask / _mask, obj_cls_raw_acc,
+    obj_cls_pre_acc / _unmask / _mask; every other ratio is hits / float(count + 1e-8).  The key set of the first
+    update holds until `reset()`.
+
+    `txt_lm_cls_logits` is the (B, L, V) tensor or a `LazyLMLogits`; for the latter the hit count comes from the words a
+    loss filled under `self.sink()` (optim/loss/fused_lm_loss.hits_sink: no second GEMM), else from `materialize()`.
+    The lazy path counts the rows the loss trains on (label != -1 and inside the vocabulary).  An object-head
+    `LazyLMLogits` (training mode) is materialised under no_grad.
+    `obj_masks` / `obj_sem_masks` are taken as the bool tensors of MaskDatasetWrapper's `obj_fts` branch; integer masks
+    count as nonzero = true.  (The reference itself would INDEX, not mask, with an int64 `obj_sem_masks`: no parity
+    target.)  `keys`: compute only these (then `target_metric` is the mean of the computed ratios)."""
+    KEYS = ("og_acc", "lang_cls_acc_mask", "obj_cls_post_acc", "obj_cls_post_acc_unmask", "obj_cls_post_acc_mask",
+            "obj_cls_raw_acc", "obj_cls_pre_acc", "obj_cls_pre_acc_unmask", "obj_cls_pre_acc_mask")
+    _OG, _LANG, _POST, _RAW, _PRE = range(5)
+
+    def __init__(self, device: torch.device | str = "cuda", keys=None):
+        from .common import cls_hits
+        self.words = torch.zeros((5, cls_hits.WORDS), dtype=torch.int64, device=device)
+        n = len(self.KEYS) + 1
+        self._last = torch.zeros(n, dtype=torch.float64, device=device)
+        self._acc = torch.zeros(n, dtype=torch.float64, device=device)
+        self._total = torch.zeros(1, dtype=torch.float64, device=device)
+        if keys is not None:
+            keys = tuple(keys)
+            bad = [k for k in keys if k not in self.KEYS + ("target_metric",)]
+            if bad:
+                raise ValueError(f"PretrainCounter: unknown keys {bad}")
+        self.keys = keys
+        self._order = None                         # the keys of the fold's terms, fixed by the first update
+        self._sink = None
+
+    def reset(self) -> None:
+        for t in (self.words, self._last, self._acc, self._total):
+            t.zero_()
+        self._order = None
+        if self._sink is not None:
+            self._sink.launches = 0
+
+    def sink(self):
+        """Context for the loss evaluation: a fused masked-LM loss inside it adds its hit count to this counter's words."""
+        from .optim.loss import fused_lm_loss as F_lm
+        if self._sink is None:
+            self._sink = F_lm.HitsSink(self.words[self._LANG])
+        return F_lm.hits_sink(self._sink)
+
+    def _wanted(self, key: str) -> bool:
+        return self.keys is None or key in self.keys
+
+    def update(self, data_dict: dict) -> None:
+        from .common import cls_hits
+        dev = self.words.device
+        lm = data_dict["txt_lm_cls_logits"]
+        lm_lazy = hasattr(lm, "materialize")
+        _need_gpu("PretrainCounter", self.words, lm.hidden if lm_lazy else lm)
+        B = int(lm.shape[0])
+        w = self.words
+        word = lambda s, i: w[s, i:i + 1]  # noqa: E731
+        problems, terms, order = [], [], []
+        eps = 1e-8
+
+        def obj_logits(key):
+            x = data_dict[key]
+            if hasattr(x, "materialize"):
+                with torch.no_grad():
+                    x = x.materialize()
+            return x
+
+        if "tgt_object_id" in data_dict and "og3d_logits" in data_dict and self._wanted("og_acc"):
+            tgt = data_dict["tgt_object_id"]
+            problems.append(cls_hits.problem(data_dict["og3d_logits"], tgt, w[self._OG]))
+            terms.append(cls_hits.term(word(self._OG, 0), word(self._OG, 1), const_denominator=float(len(tgt))))
+            order.append("og_acc")
+        if self._wanted("lang_cls_acc_mask"):
+            filled = lm_lazy and self._sink is not None and self._sink.launches > 0
+            if filled:
+                self._sink.launches = 0             # the loss has added this batch's hits to the words already
+            else:
+                if lm_lazy:
+                    with torch.no_grad():
+                        lm = lm.materialize()
+                problems.append(cls_hits.problem(lm, data_dict["masked_lm_labels"], w[self._LANG], ignore_index=-1))
+            terms.append(cls_hits.term(word(self._LANG, 0), word(self._LANG, 1), eps=eps))
+            order.append("lang_cls_acc_mask")
+        for key, slot, split in (("obj_cls_post", self._POST, True), ("obj_cls_raw", self._RAW, False),
+                                 ("obj_cls_pre", self._PRE, True)):
+            if f"{key}_logits" not in data_dict:
+                continue
+            names = [f"{key}_acc"] + ([f"{key}_acc_unmask", f"{key}_acc_mask"] if split else [])
+            names = [n for n in names if self._wanted(n)]
+            if not names:
+                continue
+            use_split = split and any(n != f"{key}_acc" for n in names)
+            problems.append(cls_hits.problem(obj_logits(f"{key}_logits"), data_dict["obj_labels"], w[slot],
+                                             sel=data_dict["obj_masks"],
+                                             split_a=data_dict["obj_sem_masks"] if use_split else None))
+            for n in names:
+                if n.endswith("_unmask"):
+                    terms.append(cls_hits.term(word(slot, 2), word(slot, 3), eps=eps))
+                elif n.endswith("_mask"):
+                    terms.append(cls_hits.term(word(slot, 0), word(slot, 1), word(slot, 2), word(slot, 3), eps=eps))
+                else:
+                    terms.append(cls_hits.term(word(slot, 0), word(slot, 1), eps=eps))
+                order.append(n)
+        if self._order is None:
+            self._order = tuple(order)
+        elif self._order != tuple(order):
+            raise ValueError(f"PretrainCounter: this batch gives the keys {order}, the updates since the last reset gave "
+                             f"{list(self._order)} (reset() the counter first)")
+        cls_hits.launch(problems, dev)
+        cls_hits.fold(terms, float(B), len(terms), self._last, self._acc, self._total)
+
+    def _names(self):
+        return list(self._order or ()) + ["target_metric"]
+
+    def last(self) -> dict:
+        """The last batch's `batch_metrics` ratios: {key: 0-dim float64 device tensor} (clones; no host sync)."""
+        if self._order is None:
+            return {}
+        vals = self._last[:len(self._order) + 1].clone()
+        return {k: vals[i] for i, k in enumerate(self._names()) if self._wanted(k)}
+
+    def result(self) -> dict:
+        """`record()`: per key the batch ratios weighted by their B, over the total B.  The one read-back."""
+        if self._order is None:
+            return {}
+        n = len(self._order) + 1
+        vals = torch.cat([self._acc[:n], self._total]).tolist()
+        total = vals[-1]
+        return {k: vals[i] / total for i, k in enumerate(self._names()) if self._wanted(k)}
+
+
+class ReferIt3DCounter:
+    """ReferIt3DEval.batch_metrics(include_count=True) with BaseEvaluator.update / record (evaluator/referit3d_eval.py:
+    14-83, evaluator/build.py:26-41) as integer counts on the device: one gps_cls_hits launch per `update`, no host
+    sync (an update can be captured); `result()` is the one read-back.
+
+    og_acc with _easy / _hard (`is_hard`) and _view_dep / _view_indep (`is_view_dependent`) from ONE problem with both
+    splits; txt_acc when `txt_cls_logits` is there; `<key>_acc` for every 3-D `*logits` tensor whose leading shape is
+    `obj_labels`'s (hits among `obj_masks`, count `obj_masks.sum()`).  Per-scene (B, L, O) `og3d_logits` with (B, L)
+    targets are flattened as the reference does (:16-20)."""
+    _MAX_KEYS = 16
+
+    def __init__(self, device: torch.device | str = "cuda"):
+        from .common import cls_hits
+        self.words = torch.zeros((self._MAX_KEYS, cls_hits.WORDS), dtype=torch.int64, device=device)
+        self._slots = {}                           # problem name -> row of `words`
+
+    def reset(self) -> None:
+        self.words.zero_()
+        self._slots = {}
+
+    def _slot(self, name: str) -> torch.Tensor:
+        if name not in self._slots:
+            if len(self._slots) >= self._MAX_KEYS:
+                raise ValueError(f"ReferIt3DCounter: more than {self._MAX_KEYS} logits tensors")
+            self._slots[name] = len(self._slots)
+        return self.words[self._slots[name]]
+
+    def update(self, data_dict: dict) -> None:
+        from . import _native
+        from .common import cls_hits
+        og = data_dict["og3d_logits"]
+        _need_gpu("ReferIt3DCounter", self.words, og)
+        tgt, hard, view = data_dict["tgt_object_id"], data_dict["is_hard"], data_dict["is_view_dependent"]
+        if og.dim() == 3:                            # per-scene evaluation
+            og = og.flatten(0, 1)
+        problems = [cls_hits.problem(og, tgt, self._slot("og_acc"), split_a=hard, split_b=view)]
+        if "txt_cls_logits" in data_dict:
+            problems.append(cls_hits.problem(data_dict["txt_cls_logits"], data_dict["tgt_object_label"],
+                                             self._slot("txt_acc")))
+        gt, mask = data_dict["obj_labels"], data_dict["obj_masks"]
+        for key, x in data_dict.items():
+            if (key.endswith("logits") and torch.is_tensor(x) and x.dim() == 3 and x.shape[:2] == gt.shape
+                    and not (key == "og3d_logits")):
+                problems.append(cls_hits.problem(x, gt, self._slot(key.replace("logits", "acc")), sel=mask))
+        dev = self.words.device
+        for i in range(0, len(problems), _native.CLS_HITS_MAX_PROBLEMS):
+            cls_hits.launch(problems[i:i + _native.CLS_HITS_MAX_PROBLEMS], dev)
+
+    def result(self, include_count: bool = False) -> dict:
+        """The reference's keys: (hits, count) pairs, or the ratios hits / max(count, 1)."""
+        rows = self.words[:max(len(self._slots), 1)].tolist()
+        pairs = {}
+        for name, s in self._slots.items():
+            h, c, ha, ca, hb, cb = rows[s]
+            if name == "og_acc":
+                pairs.update({"og_acc_easy": (h - ha, c - ca), "og_acc_hard": (ha, ca), "og_acc_view_dep": (hb, cb),
+                              "og_acc_view_indep": (h - hb, c - cb), "og_acc": (h, c)})
+            else:
+                pairs[name] = (h, c)
+        if include_count:
+            return pairs
+        return {k: h / max(n, 1) for k, (h, n) in pairs.items()}
+
+
+class ObjClsCounter:
+    """PretrainObjEval (evaluator/objcls_eval.py:14-23): `accuracy` over `obj_logits[obj_masks]`, as two integers on the
+    device (one gps_cls_hits launch per `update`, no host sync; `result()` is the one read-back)."""
+
+    def __init__(self, device: torch.device | str = "cuda"):
+        from .common import cls_hits
+        self.words = torch.zeros(cls_hits.WORDS, dtype=torch.int64, device=device)
+
+    def reset(self) -> None:
+        self.words.zero_()
+
+    def update(self, data_dict: dict) -> None:
+        from .common import cls_hits
+        x = data_dict["obj_logits"]
+        _need_gpu("ObjClsCounter", self.words, x)
+        cls_hits.launch([cls_hits.problem(x, data_dict["obj_labels"], self.words, sel=data_dict["obj_masks"])],
+                        self.words.device)
+
+    def result(self, include_count: bool = False) -> dict:
+        h, c = self.words[:2].tolist()
+        return {"accuracy": (h, c) if include_count else h / max(c, 1)}
 
 
 def _answer_hits(answer_scores: torch.Tensor, answer_label: torch.Tensor, k: int = 10):

@@ -15,9 +15,14 @@ is only known on the device:
 
 Loss value and every gradient equal the reference formulation's (to bf16 rounding of the logits); full logits exist
 only when somebody asks for them (`LazyLMLogits.materialize()`: evaluation, accuracy metrics).
+
+The masked-LM accuracy of the reference's per-step `PretrainEval.batch_metrics` (evaluator/pretrain_eval.py:27-29)
+needs none of that: inside `hits_sink(words)` the forward pass adds the arg-max hit count of the labelled rows it has
+just computed to six int64 counter words (one extra gps_cls_hits launch behind the cross-entropy forward launch).
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Optional
 
 import torch
@@ -35,6 +40,37 @@ def _ticket(device: torch.device) -> torch.Tensor:
     if t is None:
         t = _TICKETS[key] = torch.zeros(1, dtype=torch.int32, device=device)
     return t
+
+
+class HitsSink:
+    """Where `_SparseLMLoss.forward` adds its hit counts: `words` = 6 int64 counter words of gps_cls_hits (hits and
+    labelled rows in the first two); `launches` counts the forward passes that have added to them.  With `keep` set the
+    last forward pass also leaves `saved` = (labelled-row logits (n, Vp) bf16, their labels, n_valid, V) for tests that
+    restate the count (the tensors are the loss's own: they hold their values until its backward pass has run)."""
+
+    def __init__(self, words: torch.Tensor):
+        if not (words.is_cuda and words.dtype == torch.int64 and words.numel() == 6 and words.is_contiguous()):
+            raise ValueError("hits_sink: the counter must be 6 contiguous int64 words on a GPU")
+        self.words, self.launches = words, 0
+        self.keep, self.saved = False, None
+
+
+_HITS_SINK: Optional[HitsSink] = None
+
+
+@contextlib.contextmanager
+def hits_sink(counter_words):
+    """Inside this context every `_SparseLMLoss.forward` issues one gps_cls_hits problem over its labelled-row logits
+    (cols = V, ld = Vp, rows_dev = n_valid) that ADDS [hits, labelled rows] to `counter_words` (6 int64 words, or a
+    `HitsSink`).  No second GEMM, no (B, L, V) tensor; outside the context the forward pass issues exactly its own
+    launches.  Yields the sink (`.launches` tells whether a loss ran under it)."""
+    global _HITS_SINK
+    sink = counter_words if isinstance(counter_words, HitsSink) else HitsSink(counter_words)
+    prev, _HITS_SINK = _HITS_SINK, sink
+    try:
+        yield sink
+    finally:
+        _HITS_SINK = prev
 
 
 def _padded_shadow(weight: torch.Tensor, bias: Optional[torch.Tensor]):
@@ -134,6 +170,15 @@ class _SparseLMLoss(torch.autograd.Function):
                                                 n_valid.data_ptr(), rows.data_ptr(), lse.data_ptr(), mean.data_ptr(),
                                                 _ticket(dev).data_ptr(), torch.cuda.current_stream().cuda_stream)
         _native.check(st, "masked_ce_forward")
+        sink = _HITS_SINK
+        if sink is not None:
+            # the masked-LM hit count of the rows just computed: columns [V, Vp) are padding and never candidates
+            from ...common import cls_hits
+            cls_hits.launch([cls_hits.problem(logits, lp, sink.words, ignore_index=int(ignore_index), rows_dev=n_valid,
+                                              cols=V)], dev)
+            sink.launches += 1
+            if sink.keep:
+                sink.saved = (logits, lp, n_valid, V)
         ctx.save_for_backward(hp, w16, logits, lp, lse, perm, n_valid, mean)
         ctx.meta = (n, D, V, Vp, int(ignore_index), h.dtype, bias is not None)
         ctx.prepermuted = plan is not None
