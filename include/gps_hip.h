@@ -470,6 +470,55 @@ GPS_API int gps_bce_logits_backward(int rows, int cols, int x_bf16, const void *
                                     const void *y, const unsigned char *w, float scale, const float *grad_out, void *dx,
                                     long long ld_dx, gps_stream_t stream);
 
+/* ---- grounding: the tail of a get_mlp_head stack and the og3d cross entropy (gps_ground.hip) -----------------------------
+ * get_mlp_head (modules/utils.py) = Linear -> ReLU -> LayerNorm(eps 1e-12) -> Dropout -> Linear; the four stacks of
+ * GroundHeadV1 (modules/heads/grounding_head.py:20-27).  gps_mlp_tail_forward is everything behind the first Linear:
+ *   h (n_rows, d) bf16 (h_bf16 != 0) or fp32, row pitch ld_h >= d elements, read in place.  ReLU is applied here; it is
+ *   idempotent, so h may be the output of a bias + ReLU GEMM epilogue.
+ *   z[r][c] = dropout(LayerNorm(relu(h[r]); gamma, beta, eps))[c];  dropout index law: element (r, c) draws
+ *   rng_u32(effective_seed(seed, seed_dev), r * d + c) (csrc/gps_dropout.h; seed_dev = optional device word, may be NULL)
+ *   -- the logical index, whatever ld_h is --, is kept iff the value >= drop_threshold(p_drop), then scaled by
+ *   1 / (1 - p_drop); p_drop = 0: no dropout.
+ *   outputs, one or both: z16 (n_rows, d) bf16 contiguous = bf16(z), the input of a following class Linear;
+ *   logit (n_rows) fp32 = <z[r], w2> + b2[0] from the UNROUNDED z (the 1-output last Linear; w2 (d), b2 (1) fp32), and
+ *   exactly -inf where keep[r] == 0 (keep: n_rows bytes or NULL = all kept; it touches the logit only).
+ *   mean, rstd (n_rows) fp32 are saved for the backward pass.  A row with no positive entry has variance 0:
+ *   rstd = rsqrt(eps), z = dropout(beta), all finite.
+ * Shapes served: d a multiple of 8 with 8 <= d <= 1024, any n_rows >= 0, ld_h a multiple of 8, 16-byte aligned h / gamma /
+ * beta / w2 / z16; anything else GPS_ERR_UNSUPPORTED.  NULL mandatory pointers, ld_h < d, p_drop outside [0, 1):
+ * GPS_ERR_INVALID_ARGUMENT.  n_rows = 0: GPS_OK, nothing launched.
+ * gps_mlp_tail_backward, from dlogit (n_rows) fp32 and / or dz16 (n_rows, d) bf16 (one of them may be NULL), the same h,
+ * mean, rstd and the same seed (the mask is recomputed, never stored):
+ *   dpre (n_rows, d) in h's dtype, row pitch ld_dpre (columns past d are not written): the gradient with respect to h,
+ *   already multiplied by [h > 0] -- behind a bias + ReLU GEMM epilogue that is the first Linear's output gradient;
+ *   dgamma, dbeta (d) fp32; dw2 (d), db2 (1) fp32 (mandatory with dlogit, else optional).  Rows with keep[r] == 0
+ *   take no gradient from dlogit, whatever it holds there.
+ *   partial: gps_mlp_tail_partial_rows(n_rows) * (3 d + 4) floats of scratch; ticket: one unsigned int per call site, ZERO
+ *   before the first launch and left zero.  The parameter gradients are per-workgroup partial rows added in index order by
+ *   the last workgroup to arrive: no float atomics, run-to-run identical. */
+GPS_API int gps_mlp_tail_partial_rows(int n_rows);
+GPS_API int gps_mlp_tail_forward(int n_rows, int d, int h_bf16, const void *h, long long ld_h, const float *gamma,
+                                 const float *beta, float eps, float p_drop, unsigned long long seed,
+                                 const unsigned long long *seed_dev, const float *w2, const float *b2,
+                                 const unsigned char *keep, void *z16, float *logit, float *mean, float *rstd,
+                                 gps_stream_t stream);
+GPS_API int gps_mlp_tail_backward(int n_rows, int d, int h_bf16, const void *h, long long ld_h, const float *gamma,
+                                  const float *beta, const float *mean, const float *rstd, float p_drop,
+                                  unsigned long long seed, const unsigned long long *seed_dev, const float *w2,
+                                  const unsigned char *keep, const float *dlogit, const void *dz16, void *dpre,
+                                  long long ld_dpre, float *dgamma, float *dbeta, float *dw2, float *db2, float *partial,
+                                  unsigned int *ticket, gps_stream_t stream);
+/* og3d_loss (optim/loss/loss.py:8-9) = F.cross_entropy(logits (B, O) fp32 with row pitch ld, target (B) int64) with torch's
+ * defaults: loss[0] = mean over the rows whose target is not ignored of lse(x_b) - x_b[target_b]; -inf entries allowed
+ * (the padded objects).  target -100 (torch's ignore_index) and any other value outside [0, O) count as ignored.
+ * dlogits (B, O) fp32 contiguous = the unit logit gradient (softmax - onehot) / n_valid, exactly 0 at -inf entries and in
+ * ignored rows: the backward pass is one elementwise scale.  A row whose entries are all -inf makes the loss NaN, no
+ * valid row too, as torch does.  1 <= O <= 512 (else GPS_ERR_UNSUPPORTED); B = 0: GPS_OK, nothing written.
+ * partial: gps_og3d_ce_partial_floats(B) floats; ticket as above; the mean is a fixed-order sum of workgroup partials. */
+GPS_API int gps_og3d_ce_partial_floats(int B);
+GPS_API int gps_og3d_ce_forward(int B, int O, const float *logits, long long ld, const long long *target, float *loss,
+                                float *dlogits, float *partial, unsigned int *ticket, gps_stream_t stream);
+
 /* ---- y = x / max(||x||_2, eps) per row and its backward ------------------------------------------------------------
  * Replaces F.normalize(x, dim=-1, p=2) in the contrastive losses (optim/loss/contra_loss.py:38-39, 60, 82-83): torch runs
  * norm, clamp, expand, div forward and seven elementwise / reduction kernels backward.  x, y, dy, dx (n_rows, d) fp32

@@ -170,6 +170,12 @@ SIGNATURES = {
     "gps_bce_logits_partial_floats": [_i, _i],
     "gps_bce_logits_forward": [_i, _i, _i, _vp, ctypes.c_longlong, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp],
     "gps_bce_logits_backward": [_i, _i, _i, _vp, ctypes.c_longlong, _i, _vp, _vp, _f, _vp, _vp, ctypes.c_longlong, _vp],
+    "gps_mlp_tail_partial_rows": [_i],
+    "gps_mlp_tail_forward": [_i, _i, _i, _vp, ctypes.c_longlong, _vp, _vp, _f, _f, ctypes.c_ulonglong] + [_vp] * 9,
+    "gps_mlp_tail_backward": [_i, _i, _i, _vp, ctypes.c_longlong, _vp, _vp, _vp, _vp, _f, ctypes.c_ulonglong]
+                             + [_vp] * 6 + [ctypes.c_longlong] + [_vp] * 7,
+    "gps_og3d_ce_partial_floats": [_i],
+    "gps_og3d_ce_forward": [_i, _i, _vp, ctypes.c_longlong] + [_vp] * 6,
     "gps_clip_loss_forward": [_i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "gps_clip_loss_backward": [_i, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                _vp],

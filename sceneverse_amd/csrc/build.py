@@ -23,6 +23,7 @@ SOURCES = [
     ("gps_losses.hip", []),
     ("gps_contrastive.hip", []),
     ("gps_qa.hip", []),
+    ("gps_ground.hip", []),
     ("gps_layernorm.hip", []),
     ("gps_objects.hip", []),
     ("gps_refer.hip", ["-ffp-contract=off"]),

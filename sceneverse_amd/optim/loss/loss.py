@@ -29,7 +29,18 @@ def _w_unmasked(d):
     return d["obj_masks"] * d["obj_sem_masks"]
 
 
+# True = og3d_loss on csrc/gps_ground.hip for 2-D GPU logits.  Off by default: inside the captured fine-tune step the native
+# launch did not beat F.cross_entropy by more than the spread between repeated windows
+_FUSED_OG3D = False
+
+
 def og3d_loss(data_dict):                                   # ref :8-9
+    logits, tgt = data_dict["og3d_logits"], data_dict["tgt_object_id"]
+    if _FUSED_OG3D and logits.is_cuda:
+        # one launch: the loss and its logit gradient, -inf at the padded objects allowed (csrc/gps_ground.hip)
+        from .fused_og3d import og3d_ce, og3d_ce_usable
+        if og3d_ce_usable(logits, tgt):
+            return og3d_ce(logits, tgt)
     return F.cross_entropy(data_dict["og3d_logits"], data_dict["tgt_object_id"].squeeze(1))
 
 
