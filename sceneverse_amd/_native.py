@@ -272,3 +272,18 @@ def check(status: int, what: str) -> None:
     msg = lib.gps_error_string(status).decode()
     hip = lib.gps_last_hip_error().decode()
     raise GpsNativeError(f"{what}: {msg}" + (f" [{hip}]" if hip else ""))
+
+
+_TICKETS = {}
+
+
+def ticket(device, site: str):
+    """The arrival counter (one zeroed int32 word) of the kernels of call site `site` on `device`: the last-arrival
+    hand-off of csrc/gps_dev.h wants a word that is zero before the first launch -- every launch leaves it at zero --
+    and carries one launch at a time, so every site has its own word per device and launches on its stream only."""
+    import torch
+    key = (device.index if device.index is not None else torch.cuda.current_device(), site)
+    t = _TICKETS.get(key)
+    if t is None:
+        t = _TICKETS[key] = torch.zeros(1, dtype=torch.int32, device=device)
+    return t

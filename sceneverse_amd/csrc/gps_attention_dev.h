@@ -2,10 +2,13 @@
 // fp32 / fp8 kernels of _ex take the workgroup mapping and the lane-group reductions).  MFMA fragment conventions of
 // v_mfma_f32_16x16x32_bf16 with lane = (m = lane & 15, g = lane >> 4): an A / B operand holds 8 bf16 of row / column m,
 // a D fragment holds rows 4 g + 0..3 of column m.  Every helper is __forceinline__: a kernel compiles to the same
-// instructions as with a private copy (tools/asm_audit.py --digest shows it).
+// instructions as with a private copy (tools/asm_audit.py --digest shows it).  pack2 / bf2f are the library's one pair
+// (gps_dev.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "gps_dev.h"
 
 namespace gps_attn_dev {
 
@@ -15,7 +18,6 @@ typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 typedef __attribute__((ext_vector_type(4))) _Float16 f16x4;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
 
 constexpr int DH = 64;                           // head width (the only one the GPS configs use)
 constexpr int KS = DH + 8;                       // LDS row pitch of row-major Q / K / V / dO tiles, bf16 elements (144 B: conflict-free b128)
@@ -24,14 +26,11 @@ constexpr float kLn2 = 0.6931471805599453f;
 constexpr float kC = 0.125f * kLog2e;            // base-2 logit per unit of q . k
 constexpr float kClamp2 = -19.931568569324174f;  // log2(1e-6)
 
-__device__ __forceinline__ unsigned int pack2(float lo, float hi) {     // v_cvt_pk_bf16_f32: round to nearest even
-  const bf16x2_t h = {(__bf16)lo, (__bf16)hi};
-  return __builtin_bit_cast(unsigned int, h);
-}
+using gps_dev::bf2f;
+using gps_dev::pack2;       // v_cvt_pk_bf16_f32: round to nearest even
 __device__ __forceinline__ bf16x8 as_frag(u32x4 v) { return __builtin_bit_cast(bf16x8, v); }
 __device__ __forceinline__ u32x4 zero4() { u32x4 z = {0u, 0u, 0u, 0u}; return z; }
 __device__ __forceinline__ f32x4 zero_acc() { f32x4 z = {0.f, 0.f, 0.f, 0.f}; return z; }
-__device__ __forceinline__ float bf2f(unsigned int bits16) { return __uint_as_float(bits16 << 16); }
 __device__ __forceinline__ f32x4 mfma32(bf16x8 a, bf16x8 b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }

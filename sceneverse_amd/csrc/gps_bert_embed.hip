@@ -19,30 +19,18 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "gps_hip.h"
+#include "gps_dev.h"
 #include "gps_dropout.h"
+#include "gps_hip.h"
 
 namespace gps_bert_embed {
 
+using namespace gps_dev;
 using namespace gps_dropout;
 
 constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / 64;
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-__device__ __forceinline__ unsigned int pack2(float lo, float hi) {   // round to nearest even (v_cvt_pk_bf16_f32)
-  return (unsigned int)__builtin_bit_cast(uint16_t, (__bf16)lo) | ((unsigned int)__builtin_bit_cast(uint16_t, (__bf16)hi) << 16);
-}
-// keep * scale of the 4 elements starting at element index e0 (1 everywhere without dropout)
-__device__ __forceinline__ float4 keep4(unsigned int thr, float scale, unsigned long long seed, unsigned long long e0) {
-  if (thr == 0u) return make_float4(1.f, 1.f, 1.f, 1.f);
-  return make_float4(rng_u32(seed, e0 + 0) >= thr ? scale : 0.f, rng_u32(seed, e0 + 1) >= thr ? scale : 0.f,
-                     rng_u32(seed, e0 + 2) >= thr ? scale : 0.f, rng_u32(seed, e0 + 3) >= thr ? scale : 0.f);
-}
 // (word[id] + type) + pos[p] for the 4 columns at c0: HF's order of the two additions
 __device__ __forceinline__ float4 gather4(const float *__restrict__ w, const float *__restrict__ p, const float *__restrict__ t,
                                           int c0) {
@@ -67,8 +55,7 @@ __global__ __launch_bounds__(kBlock) void fwd_kernel(int n_rows, int d, const in
   // a plan built from masks that break its precondition (gps_varlen_plan's violation word): every row leaves as NaN, so
   // that the loss of the step is NaN instead of silently wrong
   const float poison = (poison_dev && *poison_dev != 0) ? __builtin_nanf("") : 1.f;
-  const float scale = thr ? 1.f / (1.f - p_drop) : 1.f;
-  const unsigned long long sd = seed + ((thr && seed_dev) ? *seed_dev : 0ull);
+  const Drop dr{thr, thr ? 1.f / (1.f - p_drop) : 1.f, seed + ((thr && seed_dev) ? *seed_dev : 0ull)};
   const float inv_d = 1.f / (float)d;
   for (int row = blockIdx.x * kWaves + wave; row < n_rows; row += gridDim.x * kWaves) {
     const float *w = word + (size_t)ids[row] * d, *p = pos_tab + (size_t)pos[row] * d;
@@ -94,14 +81,14 @@ __global__ __launch_bounds__(kBlock) void fwd_kernel(int n_rows, int d, const in
       const int c0 = (i * 64 + lane) * 4;
       const float4 g = *reinterpret_cast<const float4 *>(gamma + c0);
       const float4 bt = *reinterpret_cast<const float4 *>(beta + c0);
-      const float4 k = keep4(thr, scale, sd, base + c0);
+      const float4 k = drop_factor4(dr, base + c0);
       float4 o;
       o.x = ((z[i].x - mean) * rstd * g.x + bt.x) * k.x;
       o.y = ((z[i].y - mean) * rstd * g.y + bt.y) * k.y;
       o.z = ((z[i].z - mean) * rstd * g.z + bt.z) * k.z;
       o.w = ((z[i].w - mean) * rstd * g.w + bt.w) * k.w;
       *reinterpret_cast<float4 *>(y + base + c0) = o;
-      if (y16) *reinterpret_cast<uint2 *>(y16 + base + c0) = make_uint2(pack2(o.x, o.y), pack2(o.z, o.w));
+      if (y16) store4(y16 + base, c0, o);
     }
   }
 }
@@ -119,8 +106,7 @@ __global__ __launch_bounds__(kBlock) void bwd_kernel(int n_rows, int d, const fl
   extern __shared__ float red[];      // [kWaves][d], used for dgamma then dbeta
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int n_live = rows_dev ? min(n_rows, *rows_dev) : n_rows;
-  const float scale = thr ? 1.f / (1.f - p_drop) : 1.f;
-  const unsigned long long sd = seed + ((thr && seed_dev) ? *seed_dev : 0ull);
+  const Drop dr{thr, thr ? 1.f / (1.f - p_drop) : 1.f, seed + ((thr && seed_dev) ? *seed_dev : 0ull)};
   const float inv_d = 1.f / (float)d;
   float4 gacc[ITERS], bacc[ITERS], gm[ITERS];
 #pragma unroll
@@ -149,7 +135,7 @@ __global__ __launch_bounds__(kBlock) void bwd_kernel(int n_rows, int d, const fl
         g.x += __uint_as_float(u.x << 16); g.y += __uint_as_float(u.x & 0xFFFF0000u);
         g.z += __uint_as_float(u.y << 16); g.w += __uint_as_float(u.y & 0xFFFF0000u);
       }
-      const float4 k = keep4(thr, scale, sd, base + c0);
+      const float4 k = drop_factor4(dr, base + c0);
       g = make_float4(g.x * k.x, g.y * k.y, g.z * k.z, g.w * k.w);         // gradient of the LayerNorm output
       const float4 e = gather4(w, p, type_row, c0);
       zh[i] = make_float4((e.x - mean) * rstd, (e.y - mean) * rstd, (e.z - mean) * rstd, (e.w - mean) * rstd);
@@ -613,6 +599,8 @@ __global__ __launch_bounds__(256) void joint_embed_bwd_kernel(int n, int d4, int
 
 }  // namespace gps_rowplan
 
+using gps_dev::aligned16;
+using gps_dev::launch_status;
 
 extern "C" {
 
@@ -645,7 +633,7 @@ int gps_bert_embed_forward(int n_rows, int d, const long long *ids, const long l
     default: return GPS_ERR_UNSUPPORTED;
   }
 #undef GPS_BE_FWD
-  return hipGetLastError() == hipSuccess ? GPS_OK : GPS_ERR_LAUNCH;
+  return launch_status();
 }
 
 int gps_bert_position_grad(int n_seq, int n_pos, int d, const int *cu_rows, const float *dz, float *out, gps_stream_t stream) {
@@ -653,7 +641,7 @@ int gps_bert_position_grad(int n_seq, int n_pos, int d, const int *cu_rows, cons
   if (n_seq < 0 || n_pos < 0 || d < 1) return GPS_ERR_INVALID_ARGUMENT;
   if ((d & 255) || d > 1024) return GPS_ERR_UNSUPPORTED;
   if (n_pos == 0) return GPS_OK;
-  if (!cu_rows || !dz || !out || (((uintptr_t)dz | (uintptr_t)out) & 15)) return GPS_ERR_INVALID_ARGUMENT;
+  if (!cu_rows || !dz || !out || !aligned16(dz) || !aligned16(out)) return GPS_ERR_INVALID_ARGUMENT;
   const size_t lds = sizeof(float) * kWaves * d;
   hipStream_t s = (hipStream_t)stream;
   switch (d >> 8) {
@@ -663,7 +651,7 @@ int gps_bert_position_grad(int n_seq, int n_pos, int d, const int *cu_rows, cons
     case 4: hipLaunchKernelGGL((pos_grad_kernel<4>), dim3(n_pos), dim3(kBlock), lds, s, n_seq, d, cu_rows, dz, out); break;
     default: return GPS_ERR_UNSUPPORTED;
   }
-  return hipGetLastError() == hipSuccess ? GPS_OK : GPS_ERR_LAUNCH;
+  return launch_status();
 }
 
 int gps_bert_embed_backward(int n_rows, int d, const float *dy, const void *dy_bf16, const long long *ids, const long long *pos,
@@ -695,7 +683,7 @@ int gps_bert_embed_backward(int n_rows, int d, const float *dy, const void *dy_b
     default: return GPS_ERR_UNSUPPORTED;
   }
 #undef GPS_BE_BWD
-  return hipGetLastError() == hipSuccess ? GPS_OK : GPS_ERR_LAUNCH;
+  return launch_status();
 }
 
 int gps_varlen_plan(const gps_varlen_text *texts, int n_texts, int n_seq_full, int *i32_out, long long *i64_out,
@@ -738,20 +726,20 @@ int gps_varlen_plan(const gps_varlen_text *texts, int n_texts, int n_seq_full, i
                      (int32_t *)i32_out, (int32_t *)i32_out + 3 * seq + 1);
   hipLaunchKernelGGL(varlen_plan_kernel, dim3(seq), dim3(kRowsThreads), lds, (hipStream_t)stream, A, (int32_t *)i32_out,
                      (int64_t *)i64_out, (uint8_t *)valid_out);
-  return hipGetLastError() == hipSuccess ? GPS_OK : GPS_ERR_LAUNCH;
+  return launch_status();
 }
 
 
 int gps_rows_move(int n, long long n_src_rows, long long n_dst_rows, int row_bytes, const void *src, const long long *src_idx,
                   void *dst, const long long *dst_idx, const int *n_live, int zero_dead, gps_stream_t stream) {
   if (n < 0 || n_src_rows < 1 || n_dst_rows < 1 || row_bytes < 16 || !src || !dst) return GPS_ERR_INVALID_ARGUMENT;
-  if ((row_bytes & 15) || (((uintptr_t)src | (uintptr_t)dst) & 15)) return GPS_ERR_UNSUPPORTED;
+  if ((row_bytes & 15) || !aligned16(src) || !aligned16(dst)) return GPS_ERR_UNSUPPORTED;
   if (n == 0) return GPS_OK;
   const int blocks = (n + 3) / 4 < 4096 ? (n + 3) / 4 : 4096;
   hipLaunchKernelGGL(gps_rowplan::rows_move_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, n, n_src_rows, n_dst_rows,
                      row_bytes / 16, reinterpret_cast<const uint4 *>(src), src_idx, reinterpret_cast<uint4 *>(dst), dst_idx, n_live,
                      zero_dead);
-  return hipGetLastError() == hipSuccess ? GPS_OK : GPS_ERR_LAUNCH;
+  return launch_status();
 }
 
 int gps_rows_pack2(int n_seq, int len_a, int len_b, int d, const float *a, const float *b, const long long *perm, const int *n_live,
@@ -763,7 +751,7 @@ int gps_rows_pack2(int n_seq, int len_a, int len_b, int d, const float *a, const
   hipLaunchKernelGGL(gps_rowplan::rows_pack2_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, n, d / 4, len_a + len_b, len_a,
                      reinterpret_cast<const float4 *>(a), reinterpret_cast<const float4 *>(b), perm, n_live,
                      reinterpret_cast<float4 *>(out), reinterpret_cast<uint2 *>(out16));
-  return hipGetLastError() == hipSuccess ? GPS_OK : GPS_ERR_LAUNCH;
+  return launch_status();
 }
 
 int gps_rows_unpack2(int n_seq, int len_a, int len_b, int d, const float *packed, const long long *inv, const unsigned char *valid,
@@ -775,7 +763,7 @@ int gps_rows_unpack2(int n_seq, int len_a, int len_b, int d, const float *packed
   hipLaunchKernelGGL(gps_rowplan::rows_unpack2_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, n, d / 4, len_a + len_b, len_a,
                      reinterpret_cast<const float4 *>(packed), inv, valid, reinterpret_cast<float4 *>(out_a),
                      reinterpret_cast<float4 *>(out_b));
-  return hipGetLastError() == hipSuccess ? GPS_OK : GPS_ERR_LAUNCH;
+  return launch_status();
 }
 
 int gps_joint_embed_forward(int n_seq, int len_a, int len_b, int d, const float *a, const float *b, const float *ea, const float *eb,
@@ -788,7 +776,7 @@ int gps_joint_embed_forward(int n_seq, int len_a, int len_b, int d, const float 
                      len_a, reinterpret_cast<const float4 *>(a), reinterpret_cast<const float4 *>(b),
                      reinterpret_cast<const float4 *>(ea), reinterpret_cast<const float4 *>(eb), perm, n_live,
                      reinterpret_cast<float4 *>(x), reinterpret_cast<float4 *>(e), reinterpret_cast<uint2 *>(x16));
-  return hipGetLastError() == hipSuccess ? GPS_OK : GPS_ERR_LAUNCH;
+  return launch_status();
 }
 
 int gps_joint_embed_backward(int n_seq, int len_a, int len_b, int d, const float *dx, const unsigned short *dx16, const float *de,
@@ -802,7 +790,7 @@ int gps_joint_embed_backward(int n_seq, int len_a, int len_b, int d, const float
                      len_a, reinterpret_cast<const float4 *>(dx), reinterpret_cast<const uint2 *>(dx16),
                      reinterpret_cast<const float4 *>(de), inv, valid, reinterpret_cast<float4 *>(da), reinterpret_cast<float4 *>(db),
                      reinterpret_cast<float4 *>(dea), reinterpret_cast<float4 *>(deb));
-  return hipGetLastError() == hipSuccess ? GPS_OK : GPS_ERR_LAUNCH;
+  return launch_status();
 }
 
 int gps_rows_plan(int n_seq, int seq_len, const unsigned char *valid, long long *perm, long long *inv, int *cu, int *n_live,
@@ -811,7 +799,7 @@ int gps_rows_plan(int n_seq, int seq_len, const unsigned char *valid, long long 
   if ((long long)n_seq * seq_len > (1 << 22)) return GPS_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(gps_rowplan::plan_kernel, dim3(1), dim3(gps_rowplan::kThreads), 0, (hipStream_t)stream, n_seq, seq_len,
                      valid, perm, inv, cu, n_live);
-  return hipGetLastError() == hipSuccess ? GPS_OK : GPS_ERR_LAUNCH;
+  return launch_status();
 }
 
 

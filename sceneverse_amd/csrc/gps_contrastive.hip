@@ -12,25 +12,21 @@
 // norm was clamped, torch's clamp_min semantics), and n . dn is a sum over the logits' own gradients, so no second pass
 // over the feature rows is needed.  fp32 throughout (the reference under bf16 autocast rounds the operands of the
 // einsum / matmul to bf16; the fp32 oracle port does not).  Latency-bound: 64 - 512 workgroups of 256 threads.
-// Arrival tickets: one unsigned int per loss, zero before the first launch and left zero by every launch.
+// Arrival tickets (the last-arrival hand-off of gps_dev.h): one unsigned int per loss, zero before the first launch
+// and left zero by every launch.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "gps_bce_dev.h"
+#include "gps_dev.h"
 #include "gps_hip.h"
 
 namespace gps_contra {
 
 constexpr int kBlock = 256, kWaves = 4;
 
-__device__ __forceinline__ float wave_sum(float v) {
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-  for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-  return v;
-}
+using namespace gps_dev;
+
 // sum over the workgroup, the same value in every thread; `red` = kWaves floats of LDS
 __device__ __forceinline__ float block_sum(float v, float *red) {
   v = wave_sum(v);
@@ -56,18 +52,6 @@ __device__ __forceinline__ float block_sum_n(float v, float *red) {
 // trips (4 waves: 5 / 8 of them in a row, 21.5 / 24.5 us per launch for a few MB)
 constexpr int kFwdWaves = 16;
 __device__ __forceinline__ float dot4(const float4 a, const float4 b) { return (a.x * b.x + a.y * b.y) + (a.z * b.z + a.w * b.w); }
-
-// publish `mine` as row `idx` of `rows`, take a ticket; the last of `count` arrivals returns true (thread 0 only) after
-// which rows[0 .. count) may be read with agent-scope loads.  The ticket word is left at zero.
-__device__ __forceinline__ bool publish_and_last(float *rows, int idx, float mine, unsigned int *ticket, int count) {
-  __hip_atomic_store(rows + idx, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  const unsigned int t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  const bool last = t == (unsigned int)count - 1u;
-  if (last) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  return last;
-}
-__device__ __forceinline__ float peek(const float *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // TextObjWithinBatch.  One workgroup per scene b.
@@ -148,7 +132,8 @@ __global__ __launch_bounds__(64 * NW) void text_obj_fwd_kernel(int B, int O, int
     int last = 0;
     if (lane == 0) {
       inv_t[b] = it;
-      last = publish_and_last(loss_rows, b, s, ticket, B) ? 1 : 0;
+      publish(loss_rows + b, s);
+      last = take_ticket(ticket, (unsigned int)B) ? 1 : 0;
     }
     if (!__shfl(last, 0, 64)) return;
     float total = 0.f;
@@ -175,7 +160,8 @@ __global__ __launch_bounds__(64 * NW) void text_obj_fwd_kernel(int B, int O, int
     inv_t[b] = it;
     // a label on a masked object has logit -inf: loss +inf, as F.cross_entropy gives
     const float mine = counted ? lse - (mk[lab] ? lg[lab] : -INFINITY) : 0.f;
-    last = publish_and_last(loss_rows, b, mine, ticket, B) ? 1 : 0;
+    publish(loss_rows + b, mine);
+    last = take_ticket(ticket, (unsigned int)B) ? 1 : 0;
   }
   if (!__shfl(last, 0, 64)) return;
   // the last scene to arrive: the mean, by the whole wave (lane-strided partial sums in a fixed order; one lane walking
@@ -364,7 +350,8 @@ __global__ __launch_bounds__(64 * NW) void clip_fwd_kernel(int n, int D, int nor
     inv_a[i] = ia;
     inv_b[i] = ib;
     const float mine = (lr - s * row[i]) + (lc - s * col[i]);
-    last = publish_and_last(loss_rows, i, mine, ticket, n) ? 1 : 0;
+    publish(loss_rows + i, mine);
+    last = take_ticket(ticket, (unsigned int)n) ? 1 : 0;
   }
   if (!__shfl(last, 0, 64)) return;
   float total = 0.f;                                              // the mean, by the whole wave of the last arrival
@@ -409,7 +396,10 @@ __global__ __launch_bounds__(kBlock) void clip_bwd_kernel(int n, int D, int norm
   p_col = block_sum(p_col, red);
   if (threadIdx.x < 64) {                                          // wave 0: the last arrival sums the row partials
     int last = 0;
-    if (threadIdx.x == 0) last = publish_and_last(ds_rows, i, p_row, ticket, n) ? 1 : 0;
+    if (threadIdx.x == 0) {
+      publish(ds_rows + i, p_row);
+      last = take_ticket(ticket, (unsigned int)n) ? 1 : 0;
+    }
     if (__shfl(last, 0, 64)) {
       float total = 0.f;
       for (int k = threadIdx.x; k < n; k += 64) total += peek(ds_rows + k);
@@ -454,8 +444,8 @@ __global__ __launch_bounds__(kBlock) void clip_bwd_kernel(int n, int D, int norm
 
 }  // namespace gps_contra
 
-static inline int launch_status() { return hipGetLastError() == hipSuccess ? GPS_OK : GPS_ERR_LAUNCH; }
-static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+using gps_dev::aligned16;
+using gps_dev::launch_status;
 
 extern "C" {
 

@@ -22,117 +22,27 @@
 // 1 / (1 - p).  The backward kernel recomputes the mask from the same law; it is never stored.
 //
 // Parameter gradients: every workgroup reduces its waves' register accumulators through LDS into one partial row
-// (dgamma | dbeta | dw2 | db2), the last workgroup to arrive adds the partial rows in index order: no float atomics,
-// run-to-run identical for a given n_rows.
+// (dgamma | dbeta | dw2 | db2), the last workgroup to arrive (gps_dev.h: arrive_and_last) adds the partial rows in index
+// order: no float atomics, run-to-run identical for a given n_rows.  Row access (Raw8, store8) and the wave reductions are
+// gps_dev.h's, Drop / drop_factor are gps_dropout.h's.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gps_dev.h"
 #include "gps_dropout.h"
 #include "gps_hip.h"
 
 namespace gps_ground {
 
+using namespace gps_dev;
+using gps_dropout::Drop;
+using gps_dropout::drop_factor;
 using gps_dropout::effective_seed;
-using gps_dropout::rng_u32;
 
 constexpr int kFwdBlock = 256, kFwdWaves = 4, kFwdMaxBlocks = 2048;
 constexpr int kBwdBlock = 512, kBwdWaves = 8, kBwdMaxParts = 256, kBwdRowsPerBlock = 32;
 constexpr int kCeBlock = 256, kCeWaves = 4, kCeMaxO = 512;
 constexpr int kMaxD = 1024;
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-  return v;
-}
-__device__ __forceinline__ int wave_sum_int(int v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-__device__ __forceinline__ uint32_t f2bf(float f) {                 // round to nearest even; NaN stays NaN
-  uint32_t u = __float_as_uint(f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return u >> 16;
-}
-// 8 consecutive elements as they lie in memory (conversion deferred: the loads of a row are issued together)
-template <bool BF16> struct Raw8;
-template <> struct Raw8<true> {
-  uint4 u;
-  __device__ __forceinline__ void load(const void *base, size_t idx) {
-    u = *reinterpret_cast<const uint4 *>(reinterpret_cast<const uint16_t *>(base) + idx);
-  }
-  __device__ __forceinline__ void get(float v[8]) const {
-    v[0] = __uint_as_float(u.x << 16); v[1] = __uint_as_float(u.x & 0xffff0000u);
-    v[2] = __uint_as_float(u.y << 16); v[3] = __uint_as_float(u.y & 0xffff0000u);
-    v[4] = __uint_as_float(u.z << 16); v[5] = __uint_as_float(u.z & 0xffff0000u);
-    v[6] = __uint_as_float(u.w << 16); v[7] = __uint_as_float(u.w & 0xffff0000u);
-  }
-};
-template <> struct Raw8<false> {
-  float4 a, b;
-  __device__ __forceinline__ void load(const void *base, size_t idx) {
-    const float4 *p = reinterpret_cast<const float4 *>(reinterpret_cast<const float *>(base) + idx);
-    a = p[0];
-    b = p[1];
-  }
-  __device__ __forceinline__ void get(float v[8]) const {
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-  }
-};
-template <bool BF16>
-__device__ __forceinline__ void store8(void *base, size_t idx, const float v[8]) {
-  if constexpr (BF16) {
-    uint4 u;
-    u.x = f2bf(v[0]) | (f2bf(v[1]) << 16); u.y = f2bf(v[2]) | (f2bf(v[3]) << 16);
-    u.z = f2bf(v[4]) | (f2bf(v[5]) << 16); u.w = f2bf(v[6]) | (f2bf(v[7]) << 16);
-    *reinterpret_cast<uint4 *>(reinterpret_cast<uint16_t *>(base) + idx) = u;
-  } else {
-    float4 *p = reinterpret_cast<float4 *>(reinterpret_cast<float *>(base) + idx);
-    p[0] = make_float4(v[0], v[1], v[2], v[3]);
-    p[1] = make_float4(v[4], v[5], v[6], v[7]);
-  }
-}
-__device__ __forceinline__ void load8f(const float *p, float v[8]) {
-  const float4 a = *reinterpret_cast<const float4 *>(p), b = *reinterpret_cast<const float4 *>(p + 4);
-  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-}
-// loads above this line are issued before anything below it (the compiler otherwise sinks them next to their first use)
-#define GPS_GROUND_LOADS_ISSUED() asm volatile("" ::: "memory")
-
-__device__ __forceinline__ void publish(float *p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ float peek(const float *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-// every thread's publish()ed values are in memory, then thread 0 takes a ticket: true in EVERY thread of the last of
-// `count` workgroups to arrive (`flag` = one int of LDS).  The ticket word is left at zero.
-__device__ __forceinline__ bool arrive_and_last(unsigned int *ticket, unsigned int count, int *flag) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned int t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const bool last = t == count - 1u;
-    if (last) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    *flag = last ? 1 : 0;
-  }
-  __syncthreads();
-  return *flag != 0;
-}
-
-struct Drop {
-  unsigned int thr;          // keep iff rng >= thr; 0 = no dropout
-  float scale;               // 1 / (1 - p)
-  unsigned long long seed;
-};
-// factor of element e of the LayerNorm output: 0 (dropped) or 1 / (1 - p)
-__device__ __forceinline__ float drop_factor(const Drop &dr, unsigned long long e) {
-  if (dr.thr == 0u) return 1.f;
-  return rng_u32(dr.seed, e) >= dr.thr ? dr.scale : 0.f;
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // forward.  grid-stride over the rows, one wave per row; lane l of step i holds columns (i 64 + l) 8 .. + 7 (idle past d).
@@ -156,11 +66,11 @@ __global__ __launch_bounds__(kFwdBlock) void mlp_tail_fwd_kernel(
     const int c = (i * 64 + lane) * 8;
     live[i] = c < d;
     col[i] = live[i] ? c : 0;                    // idle lanes re-read column 0 and drop the values
-    load8f(gamma + col[i], gm[i]);
-    load8f(beta + col[i], bt[i]);
+    load8<false>(gamma + col[i], 0, gm[i]);
+    load8<false>(beta + col[i], 0, bt[i]);
 #pragma unroll
     for (int k = 0; k < 8; ++k) wv[i][k] = 0.f;
-    if (logit) load8f(w2 + col[i], wv[i]);
+    if (logit) load8<false>(w2 + col[i], 0, wv[i]);
   }
   const float bias2 = logit ? b2[0] : 0.f;
   for (int row = blockIdx.x * kFwdWaves + wave; row < n_rows; row += gridDim.x * kFwdWaves) {
@@ -168,7 +78,7 @@ __global__ __launch_bounds__(kFwdBlock) void mlp_tail_fwd_kernel(
 #pragma unroll
     for (int i = 0; i < ITERS; ++i) raw[i].load(h, (size_t)row * ld_h + col[i]);
     const bool kept = !keep || keep[row] != 0;
-    GPS_GROUND_LOADS_ISSUED();
+    GPS_LOADS_ISSUED();
     float x[ITERS][8];
     float s = 0.f;
 #pragma unroll
@@ -248,11 +158,11 @@ __global__ __launch_bounds__(kBwdBlock) void mlp_tail_bwd_kernel(
     const int c = (i * 64 + lane) * 8;
     live[i] = c < d;
     col[i] = live[i] ? c : 0;
-    load8f(gamma + col[i], gm[i]);
-    load8f(beta + col[i], bt[i]);
+    load8<false>(gamma + col[i], 0, gm[i]);
+    load8<false>(beta + col[i], 0, bt[i]);
 #pragma unroll
     for (int k = 0; k < 8; ++k) wv[i][k] = 0.f;
-    if (dlogit) load8f(w2 + col[i], wv[i]);
+    if (dlogit) load8<false>(w2 + col[i], 0, wv[i]);
   }
   for (int row = blockIdx.x * kBwdWaves + wave; row < n_rows; row += gridDim.x * kBwdWaves) {
     Raw8<HB> raw[ITERS];
@@ -266,7 +176,7 @@ __global__ __launch_bounds__(kBwdBlock) void mlp_tail_bwd_kernel(
     const float mean = mean_in[row], rstd = rstd_in[row];
     float dl = dlogit ? dlogit[row] : 0.f;
     const bool kept = !keep || keep[row] != 0;
-    GPS_GROUND_LOADS_ISSUED();
+    GPS_LOADS_ISSUED();
     if (!kept) dl = 0.f;                          // masked_fill passes no gradient, whatever dlogit holds there
     float xh[ITERS][8], a[ITERS][8];
     unsigned int pos = 0u;                        // bit (8 i + k): h > 0
@@ -392,8 +302,8 @@ __global__ __launch_bounds__(kCeBlock) void og3d_ce_kernel(int B, int O, const f
     const long long ti = target[i];
     cnt += (ti >= 0 && ti < O) ? 1 : 0;
   }
-  GPS_GROUND_LOADS_ISSUED();
-  const float inv_n = 1.f / (float)wave_sum_int(cnt);              // no valid row: inf here, NaN loss below, like torch's mean
+  GPS_LOADS_ISSUED();
+  const float inv_n = 1.f / (float)wave_sum(cnt);              // no valid row: inf here, NaN loss below, like torch's mean
   float row_loss = 0.f;
   if (b < B) {                                                      // wave-uniform
     const bool valid = t >= 0 && t < O;
@@ -435,8 +345,8 @@ __global__ __launch_bounds__(kCeBlock) void og3d_ce_kernel(int B, int O, const f
 
 }  // namespace gps_ground
 
-static inline int launch_status() { return hipGetLastError() == hipSuccess ? GPS_OK : GPS_ERR_LAUNCH; }
-static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+using gps_dev::aligned16;
+using gps_dev::launch_status;
 static inline int tail_shape_status(int n_rows, int d) {
   if (n_rows < 0 || d < 1) return GPS_ERR_INVALID_ARGUMENT;
   if ((d & 7) || d < 8 || d > gps_ground::kMaxD) return GPS_ERR_UNSUPPORTED;

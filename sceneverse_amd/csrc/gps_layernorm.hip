@@ -13,81 +13,23 @@
 // One wave per row, the row (<= 2048 elements, 4 consecutive elements per lane and step, 16-byte
 // loads) stays in VGPRs: mean and variance are computed two-pass from registers, row reductions are
 // wave shuffles, no LDS in forward.  Dropout uses the same counter-based RNG as the attention core
-// (seed + optional device seed word), recomputed in backward.
+// (seed + optional device seed word), recomputed in backward: Drop / drop4 / keep_mask4 of gps_dropout.h.
+// The 4-element row access (load_raw / to_f4 / store4, bf16 stores by the cast) is gps_dev.h's.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "gps_hip.h"
+#include "gps_dev.h"
 #include "gps_dropout.h"
+#include "gps_hip.h"
 
 namespace gps_ln {
 
+using namespace gps_dev;
 using namespace gps_dropout;
 
 constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / 64;
 constexpr int kMaxIter = 8;          // D <= 8 * 256 (ITERS = D / 256 is a template parameter)
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-__device__ __forceinline__ uint16_t f2bf(float f) {      // round to nearest even (v_cvt_pk_bf16_f32)
-  return __builtin_bit_cast(uint16_t, (__bf16)f);
-}
-// 4 consecutive elements at p (element index e0), as fp32
-__device__ __forceinline__ float4 load4(const float *p, size_t e0) {
-  return *reinterpret_cast<const float4 *>(p + e0);
-}
-__device__ __forceinline__ float4 load4(const uint16_t *p, size_t e0) {
-  const uint2 v = *reinterpret_cast<const uint2 *>(p + e0);
-  return make_float4(__uint_as_float(v.x << 16), __uint_as_float(v.x & 0xFFFF0000u),
-                     __uint_as_float(v.y << 16), __uint_as_float(v.y & 0xFFFF0000u));
-}
-// the same 4 elements as they lie in memory (conversion deferred: every load of a row is issued before the first use)
-__device__ __forceinline__ float4 load_raw(const float *p, size_t e0) { return *reinterpret_cast<const float4 *>(p + e0); }
-__device__ __forceinline__ uint2 load_raw(const uint16_t *p, size_t e0) { return *reinterpret_cast<const uint2 *>(p + e0); }
-__device__ __forceinline__ float4 to_f4(float4 v) { return v; }
-__device__ __forceinline__ float4 to_f4(uint2 v) {
-  return make_float4(__uint_as_float(v.x << 16), __uint_as_float(v.x & 0xFFFF0000u),
-                     __uint_as_float(v.y << 16), __uint_as_float(v.y & 0xFFFF0000u));
-}
-template <typename T> struct Raw4 { using type = float4; };
-template <> struct Raw4<uint16_t> { using type = uint2; };
-// loads above this line are issued before anything below it (the compiler otherwise sinks them next to their first use,
-// i.e. behind the wave-uniform branches of the optional operands: one memory round trip per branch instead of one per row)
-#define GPS_LN_LOADS_ISSUED() asm volatile("" ::: "memory")
-__device__ __forceinline__ void store4(float *p, size_t e0, float4 v) {
-  *reinterpret_cast<float4 *>(p + e0) = v;
-}
-__device__ __forceinline__ void store4(uint16_t *p, size_t e0, float4 v) {
-  uint2 o;
-  o.x = (unsigned int)f2bf(v.x) | ((unsigned int)f2bf(v.y) << 16);
-  o.y = (unsigned int)f2bf(v.z) | ((unsigned int)f2bf(v.w) << 16);
-  *reinterpret_cast<uint2 *>(p + e0) = o;
-}
-
-struct Drop {
-  unsigned int thr;          // keep iff rng >= thr; 0 = no dropout
-  float scale;               // 1 / (1 - p)
-  unsigned long long seed;
-};
-__device__ __forceinline__ float4 drop4(float4 h, const Drop &d, unsigned long long e0) {
-  if (d.thr == 0u) return h;
-  h.x = rng_u32(d.seed, e0 + 0) >= d.thr ? h.x * d.scale : 0.f;
-  h.y = rng_u32(d.seed, e0 + 1) >= d.thr ? h.y * d.scale : 0.f;
-  h.z = rng_u32(d.seed, e0 + 2) >= d.thr ? h.z * d.scale : 0.f;
-  h.w = rng_u32(d.seed, e0 + 3) >= d.thr ? h.w * d.scale : 0.f;
-  return h;
-}
-
-// bit j set = element e0 + j is kept (all four when there is no dropout)
-__device__ __forceinline__ unsigned int keep4(const Drop &d, unsigned long long e0) {
-  if (d.thr == 0u) return 15u;
-  return (rng_u32(d.seed, e0 + 0) >= d.thr ? 1u : 0u) | (rng_u32(d.seed, e0 + 1) >= d.thr ? 2u : 0u) |
-         (rng_u32(d.seed, e0 + 2) >= d.thr ? 4u : 0u) | (rng_u32(d.seed, e0 + 3) >= d.thr ? 8u : 0u);
-}
 
 template <typename TX, typename TH, int ITERS>
 __global__ __launch_bounds__(kBlock) void add_dropout_ln_fwd_kernel(
@@ -130,7 +72,7 @@ __global__ __launch_bounds__(kBlock) void add_dropout_ln_fwd_kernel(
 #pragma unroll
       for (int i = 0; i < ITERS; ++i) pv[i] = *reinterpret_cast<const float4 *>(post + base + (size_t)(i * 64 + lane) * 4);
     }
-    GPS_LN_LOADS_ISSUED();
+    GPS_LOADS_ISSUED();
     // phase 2: the row lives in registers
     float4 z[ITERS];
     float s = 0.f;
@@ -208,7 +150,7 @@ __global__ __launch_bounds__(kBlock, ITERS <= 3 ? 4 : 1) void add_dropout_ln_bwd
 #pragma unroll
       for (int i = 0; i < ITERS; ++i) g2r[i] = load_raw(dy16, base + (size_t)(i * 64 + lane) * 4);
     }
-    GPS_LN_LOADS_ISSUED();
+    GPS_LOADS_ISSUED();
     // phase 2
     float4 zh[ITERS], a[ITERS];
     unsigned int keep = 0u;          // 4 bits per step: the dropout decisions, drawn once for dz -> dh below
@@ -232,7 +174,7 @@ __global__ __launch_bounds__(kBlock, ITERS <= 3 ? 4 : 1) void add_dropout_ln_bwd
       }
       const float4 xv = to_f4(xr[i]);
       float4 hv = to_f4(hr[i]);
-      const unsigned int m = keep4(dr, e0);
+      const unsigned int m = keep_mask4(dr, e0);
       keep |= m << (4 * i);
       if (dr.thr) {
         hv.x = (m & 1u) ? hv.x * dr.scale : 0.f;
@@ -286,21 +228,20 @@ __global__ __launch_bounds__(kBlock, ITERS <= 3 ? 4 : 1) void add_dropout_ln_bwd
   }
 }
 
-// out[c] = sum_r part[r][c] for the 2*d columns of the [dgamma | dbeta] partial rows
-// (part is [2][parts][d]; out is [2][d]).  Workgroup (cg, rg) owns 64 columns x one slice of the rows: its 4 waves
-// split the slice (256 contiguous bytes per row and wave, 8 rows in flight per thread), combine in LDS and write
-// one row of second-level partials; the LAST workgroup of a column group to arrive (ticket counter) adds those
-// rows in slice order, so the result does not depend on the arrival order.  scratch: [kRedSlices][2 d] floats +
-// one counter per column group, zero before the first launch and left zero by every launch.
+// emit(c, sum_r part[r][c]) for the 2*d columns c of the [dgamma | dbeta] partial rows (part is [2][parts][d]).
+// Workgroup (cg, rg) owns 64 columns x one of `slices` slices of the rows: its 4 waves split the slice (256 contiguous
+// bytes per row and wave, 8 rows in flight per thread), combine in LDS and publish one row of second-level partials; the
+// LAST workgroup of a column group to arrive (the hand-off of gps_dev.h, one ticket per column group) adds those rows
+// in slice order, so the result does not depend on the arrival order.  With one slice the workgroup emits its sum itself.
+// part2: [kRedSlices][2 d] floats, tickets: one counter per column group, zero before the first launch and left zero.
 constexpr int kRedSlices = 16;
-__global__ __launch_bounds__(kBlock) void reduce_partials_kernel(int parts, int d, const float *__restrict__ part,
-                                                                  float *__restrict__ out, float *__restrict__ part2,
-                                                                  unsigned int *__restrict__ tickets) {
+template <typename Emit>
+__device__ __forceinline__ void reduce_partials_body(const float *__restrict__ part, int parts, int slices, int d,
+                                                     float *__restrict__ part2, unsigned int *__restrict__ tickets, Emit emit) {
   __shared__ float red[kWaves][64];
   __shared__ int last;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int c = blockIdx.x * 64 + lane;           // column in [0, 2 d)
-  const int slices = gridDim.y;
   const int per = (parts + slices - 1) / slices;
   const int r_begin = blockIdx.y * per, r_end = min(parts, r_begin + per);
   float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -317,41 +258,37 @@ __global__ __launch_bounds__(kBlock) void reduce_partials_kernel(int parts, int 
   red[wave][lane] = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
   __syncthreads();
   if (slices == 1) {
-    if (wave == 0 && c < 2 * d) out[c] = (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]);
+    if (wave == 0 && c < 2 * d) emit(c, (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]));
     return;
   }
-  // Hand-off without L2 write-back / invalidate episodes (the previous kernel leaves > 100 MB dirty): the second-level
-  // rows are written through (agent-scope relaxed atomic stores = sc1), waited for, then the ticket is taken; the
-  // last arriver reads them with agent-scope loads.
   if (wave == 0) {
-    if (c < 2 * d)
-      __hip_atomic_store(part2 + (size_t)blockIdx.y * 2 * d + c, (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]),
-                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (lane == 0) {
-      const unsigned int t = __hip_atomic_fetch_add(&tickets[blockIdx.x], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      last = (t == (unsigned int)slices - 1u);
-      if (last) __hip_atomic_store(&tickets[blockIdx.x], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    if (c < 2 * d) publish(part2 + (size_t)blockIdx.y * 2 * d + c, (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]));
+    if (lane == 0) last = take_ticket(&tickets[blockIdx.x], (unsigned int)slices) ? 1 : 0;
   }
   __syncthreads();
   if (!last || wave != 0 || c >= 2 * d) return;
   // all slice rows are requested before the first add (16 independent loads in flight, not 16 round trips)
   float v[kRedSlices];
 #pragma unroll
-  for (int s = 0; s < kRedSlices; ++s)
-    v[s] = (s < slices) ? __hip_atomic_load(part2 + (size_t)s * 2 * d + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.f;
+  for (int s = 0; s < kRedSlices; ++s) v[s] = (s < slices) ? peek(part2 + (size_t)s * 2 * d + c) : 0.f;
   float sum = v[0];
 #pragma unroll
   for (int s = 1; s < kRedSlices; ++s) sum += v[s];
-  out[c] = sum;
+  emit(c, sum);
+}
+
+// one problem, out is [2][d]; gridDim.y = slices (1 without scratch)
+__global__ __launch_bounds__(kBlock) void reduce_partials_kernel(int parts, int d, const float *__restrict__ part,
+                                                                  float *__restrict__ out, float *__restrict__ part2,
+                                                                  unsigned int *__restrict__ tickets) {
+  reduce_partials_body(part, parts, gridDim.y, d, part2, tickets, [=](int c, float v) { out[c] = v; });
 }
 
 // [r4] The same reduction for MANY LayerNorms in one launch (blockIdx.z = problem): the 24 + fused residual-LayerNorm
 // backward passes of a step each ended in their own 7 us reduce launch (0.19 ms per step); their parameter gradients are
 // only needed by the optimizer, so the host defers them (modules/layers/fused_norm.py) and sums them together.  Results
-// go straight into gamma.grad / beta.grad (plain store, or added to what is there).  Same two-level scheme and the same
-// fixed summation order per problem as reduce_partials_kernel.
+// go straight into gamma.grad / beta.grad (plain store, or added to what is there).  The same fixed summation order per
+// problem; every problem has its own part2 rows and tickets.
 struct LnRedProblem {          // 40 bytes
   const float *part;           // [2][parts][d]
   float *out_g, *out_b;        // (d) each
@@ -362,62 +299,15 @@ struct LnRedArgs { LnRedProblem p[kLnRedMax]; };
 
 __global__ __launch_bounds__(kBlock) void reduce_partials_grouped_kernel(const LnRedArgs args, int d, float *__restrict__ part2_all,
                                                                           unsigned int *__restrict__ tickets_all) {
-  __shared__ float red[kWaves][64];
-  __shared__ int last;
   const LnRedProblem P = args.p[blockIdx.z];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int c = blockIdx.x * 64 + lane;           // column in [0, 2 d)
-  const int groups = gridDim.x;
-  const int parts = P.parts;
-  int slices = (parts + 63) / 64;
+  int slices = (P.parts + 63) / 64;
   slices = slices > (int)gridDim.y ? (int)gridDim.y : slices;       // this problem's slices (<= kRedSlices)
   if ((int)blockIdx.y >= slices) return;
-  float *part2 = part2_all + (size_t)blockIdx.z * kRedSlices * 2 * d;
-  unsigned int *tickets = tickets_all + (size_t)blockIdx.z * groups;
-  const int per = (parts + slices - 1) / slices;
-  const int r_begin = blockIdx.y * per, r_end = min(parts, r_begin + per);
-  float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  if (c < 2 * d) {
-    const int which = c / d, col = c - which * d;
-    const float *p = P.part + (size_t)which * parts * d + col;
-    int r = r_begin + wave;
-    for (; r + 7 * kWaves < r_end; r += 8 * kWaves) {
-#pragma unroll
-      for (int u = 0; u < 8; ++u) acc[u] += p[(size_t)(r + u * kWaves) * d];
-    }
-    for (; r < r_end; r += kWaves) acc[0] += p[(size_t)r * d];
-  }
-  red[wave][lane] = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
-  __syncthreads();
-  auto emit = [&](float v) {
-    float *dst = c < d ? P.out_g + c : P.out_b + (c - d);
-    *dst = P.accumulate ? *dst + v : v;
-  };
-  if (slices == 1) {
-    if (wave == 0 && c < 2 * d) emit((red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]));
-    return;
-  }
-  if (wave == 0) {
-    if (c < 2 * d)
-      __hip_atomic_store(part2 + (size_t)blockIdx.y * 2 * d + c, (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]),
-                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (lane == 0) {
-      const unsigned int t = __hip_atomic_fetch_add(&tickets[blockIdx.x], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      last = (t == (unsigned int)slices - 1u);
-      if (last) __hip_atomic_store(&tickets[blockIdx.x], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
-  __syncthreads();
-  if (!last || wave != 0 || c >= 2 * d) return;
-  float v[kRedSlices];
-#pragma unroll
-  for (int s2 = 0; s2 < kRedSlices; ++s2)
-    v[s2] = (s2 < slices) ? __hip_atomic_load(part2 + (size_t)s2 * 2 * d + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.f;
-  float sum = v[0];
-#pragma unroll
-  for (int s2 = 1; s2 < kRedSlices; ++s2) sum += v[s2];
-  emit(sum);
+  reduce_partials_body(P.part, P.parts, slices, d, part2_all + (size_t)blockIdx.z * kRedSlices * 2 * d,
+                       tickets_all + (size_t)blockIdx.z * gridDim.x, [&](int c, float v) {
+                         float *dst = c < d ? P.out_g + c : P.out_b + (c - d);
+                         *dst = P.accumulate ? *dst + v : v;
+                       });
 }
 
 // ---- y = x / max(||x||_2, eps) per row (F.normalize(x, p=2, dim=-1)) and its backward ---------------------------------
@@ -481,6 +371,9 @@ inline int grid_rows(int n_rows) {
 
 }  // namespace gps_ln
 
+using gps_dev::aligned16;
+using gps_dev::launch_status;
+
 extern "C" {
 
 int gps_ln_partial_rows(int n_rows) { return gps_ln::grid_rows(n_rows); }
@@ -499,7 +392,7 @@ int gps_ln_reduce_partials(int parts, int d, const float *part, float *out, void
   unsigned int *tickets = scratch ? reinterpret_cast<unsigned int *>(part2 + (size_t)gps_ln::kRedSlices * 2 * d) : nullptr;
   hipLaunchKernelGGL(gps_ln::reduce_partials_kernel, dim3(groups, slices), dim3(gps_ln::kBlock), 0,
                      (hipStream_t)stream, parts, d, part, out, part2, tickets);
-  return hipGetLastError() == hipSuccess ? GPS_OK : GPS_ERR_LAUNCH;
+  return launch_status();
 }
 
 int gps_ln_reduce_partials_grouped(const gps_ln_reduce_problem *problems, int n_problems, int d, void *scratch,
@@ -527,7 +420,7 @@ int gps_ln_reduce_partials_grouped(const gps_ln_reduce_problem *problems, int n_
     unsigned int *tickets = reinterpret_cast<unsigned int *>(part2 + (size_t)kLnRedMax * kRedSlices * 2 * d);
     hipLaunchKernelGGL(reduce_partials_grouped_kernel, dim3(groups, max_slices, n), dim3(kBlock), 0, (hipStream_t)stream, args, d,
                        part2, tickets);
-    if (hipGetLastError() != hipSuccess) return GPS_ERR_LAUNCH;
+    if (launch_status() != GPS_OK) return GPS_ERR_LAUNCH;
   }
   return GPS_OK;
 }
@@ -543,7 +436,7 @@ int gps_l2_normalize_forward(int n_rows, int d, const float *x, float eps, float
   if (!x || !y || !inv_norm || (((uintptr_t)x | (uintptr_t)y) & 15)) return GPS_ERR_INVALID_ARGUMENT;
   hipLaunchKernelGGL(gps_ln::l2norm_fwd_kernel, dim3(gps_ln::grid_rows(n_rows)), dim3(gps_ln::kBlock), 0, (hipStream_t)stream,
                      n_rows, d, x, eps, y, inv_norm);
-  return hipGetLastError() == hipSuccess ? GPS_OK : GPS_ERR_LAUNCH;
+  return launch_status();
 }
 
 int gps_l2_normalize_backward(int n_rows, int d, const float *dy, const float *y, const float *inv_norm, float eps, float *dx,
@@ -554,7 +447,7 @@ int gps_l2_normalize_backward(int n_rows, int d, const float *dy, const float *y
   if (!dy || !y || !inv_norm || !dx || (((uintptr_t)dy | (uintptr_t)y | (uintptr_t)dx) & 15)) return GPS_ERR_INVALID_ARGUMENT;
   hipLaunchKernelGGL(gps_ln::l2norm_bwd_kernel, dim3(gps_ln::grid_rows(n_rows)), dim3(gps_ln::kBlock), 0, (hipStream_t)stream,
                      n_rows, d, dy, y, inv_norm, eps, dx);
-  return hipGetLastError() == hipSuccess ? GPS_OK : GPS_ERR_LAUNCH;
+  return launch_status();
 }
 
 int gps_add_dropout_layernorm_forward(int n_rows, int d, int x_bf16, int h_bf16, const void *x, const void *h,
@@ -605,7 +498,7 @@ int gps_add_dropout_layernorm_forward_post(int n_rows, int d, int x_bf16, int h_
   else GPS_LN_FWD(float, float);
 #undef GPS_LN_FWD
 #undef GPS_LN_FWD_I
-  return hipGetLastError() == hipSuccess ? GPS_OK : GPS_ERR_LAUNCH;
+  return launch_status();
 }
 
 int gps_add_dropout_layernorm_backward(int n_rows, int d, int x_bf16, int h_bf16, const void *dy,
@@ -674,7 +567,7 @@ int gps_add_dropout_layernorm_backward_post_acc(int n_rows, int d, int x_bf16, i
   else GPS_LN_BWD(float, float);
 #undef GPS_LN_BWD
 #undef GPS_LN_BWD_I
-  return hipGetLastError() == hipSuccess ? GPS_OK : GPS_ERR_LAUNCH;
+  return launch_status();
 }
 
 }  // extern "C"

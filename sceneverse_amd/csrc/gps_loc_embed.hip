@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gps_dev.h"
 #include "gps_hip.h"
 
 namespace gps_loc {
@@ -26,11 +27,7 @@ constexpr int kMaxK = 8;
 constexpr int kIters = 3;          // d = 768 (hidden size of every GPS stream)
 constexpr int kGridMax = 256;
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
+using gps_dev::wave_sum;
 
 // lane-resident slice of W (d, k_in) and b: columns (i * 64 + lane) * 4 + j
 struct Slice {
@@ -206,6 +203,9 @@ inline int grid_rows(int n) {
 
 }  // namespace gps_loc
 
+using gps_dev::aligned16;
+using gps_dev::launch_status;
+
 extern "C" {
 
 int gps_loc_embed_partial_rows(int n_rows) { return gps_loc::grid_rows(n_rows); }
@@ -217,7 +217,7 @@ int gps_loc_embed_forward(int n_rows, int k_in, int d, const float *x, const flo
   if (d != 256 * kIters || (k_in != 6 && k_in != 3 && k_in != 8)) return GPS_ERR_UNSUPPORTED;
   if (n_rows == 0) return GPS_OK;
   if (!x || !w || !gamma || !beta || !y || !mean || !rstd) return GPS_ERR_INVALID_ARGUMENT;
-  if (((uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)y) & 15) return GPS_ERR_UNSUPPORTED;
+  if (!aligned16(gamma) || !aligned16(beta) || !aligned16(y)) return GPS_ERR_UNSUPPORTED;
   const dim3 grid(grid_rows(n_rows) * 2 < (n_rows + kWaves - 1) / kWaves ? grid_rows(n_rows) * 2 : (n_rows + kWaves - 1) / kWaves), block(kBlock);   // <= 512: a wave keeps its weight slice for several rows
   hipStream_t s = (hipStream_t)stream;
   switch (k_in) {
@@ -225,7 +225,7 @@ int gps_loc_embed_forward(int n_rows, int k_in, int d, const float *x, const flo
     case 6: hipLaunchKernelGGL((fwd_kernel<6>), grid, block, 0, s, n_rows, d, x, w, bias, gamma, beta, eps, y, mean, rstd); break;
     default: hipLaunchKernelGGL((fwd_kernel<8>), grid, block, 0, s, n_rows, d, x, w, bias, gamma, beta, eps, y, mean, rstd); break;
   }
-  return hipGetLastError() == hipSuccess ? GPS_OK : GPS_ERR_LAUNCH;
+  return launch_status();
 }
 
 int gps_loc_embed_backward(int n_rows, int k_in, int d, const float *dy, const float *x, const float *w, const float *bias,
@@ -239,7 +239,7 @@ int gps_loc_embed_backward(int n_rows, int k_in, int d, const float *dy, const f
   const int sets = k_in + 3;
   if (n_rows == 0) return hipMemsetAsync(sums, 0, (size_t)sets * d * sizeof(float), s) == hipSuccess ? GPS_OK : GPS_ERR_LAUNCH;
   if (!dy || !x || !w || !gamma || !mean || !rstd || !partials) return GPS_ERR_INVALID_ARGUMENT;
-  if ((uintptr_t)dy & 15) return GPS_ERR_UNSUPPORTED;
+  if (!aligned16(dy)) return GPS_ERR_UNSUPPORTED;
   const int parts = grid_rows(n_rows);
   const size_t lds = sizeof(float) * kWaves * d;
   switch (k_in) {
@@ -248,7 +248,7 @@ int gps_loc_embed_backward(int n_rows, int k_in, int d, const float *dy, const f
     default: hipLaunchKernelGGL((bwd_kernel<8>), dim3(parts), dim3(kBlock), lds, s, n_rows, d, dy, x, w, bias, gamma, mean, rstd, partials); break;
   }
   hipLaunchKernelGGL(reduce_kernel, dim3((d + 63) / 64, sets), dim3(kBlock), 0, s, parts, sets, d, partials, sums);
-  return hipGetLastError() == hipSuccess ? GPS_OK : GPS_ERR_LAUNCH;
+  return launch_status();
 }
 
 }  // extern "C"

@@ -12,9 +12,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gps_dev.h"
 #include "gps_hip.h"
 
 namespace gps_loss {
+
+using namespace gps_dev;
 
 constexpr int kBlock = 256;
 
@@ -100,16 +103,6 @@ __global__ __launch_bounds__(kBlock) void masked_ce_bwd_kernel(int n_rows, int V
 // bench workload, one or two rounds of ~480 labelled rows); here a lane takes 8 columns per trip (15 trips), one running
 // maximum update per trip.  `rows_dev` (optional, device int): rows at or past it are DEAD -- not read, not written
 // (the masked-LM head hands the labelled rows first and its extent-aware GEMMs never read the rest).
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-
-__device__ __forceinline__ void unpack8(const u32x4 q, float (&x)[8]) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    x[2 * i] = __uint_as_float(q[i] << 16);
-    x[2 * i + 1] = __uint_as_float(q[i] & 0xFFFF0000u);
-  }
-}
-
 __global__ __launch_bounds__(kBlock) void masked_ce_fwd_vec_kernel(int n_rows, int V, const uint16_t *__restrict__ logits,
                                                                     long long ld, const int64_t *__restrict__ labels,
                                                                     long long ignore_index, const int *__restrict__ rows_dev,
@@ -128,22 +121,20 @@ __global__ __launch_bounds__(kBlock) void masked_ce_fwd_vec_kernel(int n_rows, i
   auto finish = [&](float mine) {
     if (!mean_out) { if (threadIdx.x == 0) loss[row] = mine; return; }
     if (threadIdx.x == 0) {
-      __hip_atomic_store(loss + row, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      const unsigned int t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      s_last = (t == (unsigned int)live_rows - 1u);
-      if (s_last) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      publish(loss + row, mine);
+      s_last = take_ticket(ticket, (unsigned int)live_rows);
     }
     __syncthreads();
     if (!s_last || threadIdx.x >= 64) return;
     float tot = 0.f;
     int cnt = 0;
     for (int r = threadIdx.x; r < live_rows; r += 64) {
-      tot += __hip_atomic_load(loss + r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      tot += peek(loss + r);
       const long long lb = labels[r];
       cnt += (lb != ignore_index && lb >= 0 && lb < V) ? 1 : 0;
     }
-    for (int off = 32; off >= 1; off >>= 1) { tot += __shfl_xor(tot, off, 64); cnt += __shfl_xor(cnt, off, 64); }
+    tot = wave_sum(tot);
+    cnt = wave_sum(cnt);
     if (threadIdx.x == 0) { mean_out[0] = tot / (float)cnt; mean_out[1] = (float)cnt; }
   };
   if (dead) {
@@ -252,7 +243,7 @@ __global__ __launch_bounds__(1024) void lm_row_plan_kernel(int n, int V, const i
     const long long lb = labels[i];
     mine += (lb != ignore_index && lb >= 0 && lb < V) ? 1 : 0;
   }
-  for (int off = 32; off >= 1; off >>= 1) mine += __shfl_xor(mine, off, 64);
+  mine = wave_sum(mine);
   if (lane == 0) s_cnt[w] = mine;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -288,7 +279,9 @@ __global__ __launch_bounds__(1024) void lm_row_plan_kernel(int n, int V, const i
 
 }  // namespace gps_loss
 
-static bool vec_ok(const void *p, long long ld) { return (ld % 8) == 0 && (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+static bool vec_ok(const void *p, long long ld) { return (ld % 8) == 0 && gps_dev::aligned16(p); }
+
+using gps_dev::launch_status;
 
 extern "C" {
 
@@ -312,7 +305,7 @@ int gps_masked_ce_forward_rows(int n_rows, int vocab, int logits_bf16, const voi
   else
     hipLaunchKernelGGL(gps_loss::masked_ce_fwd_kernel<float>, dim3(n_rows), dim3(gps_loss::kBlock), 0, s, n_rows,
                        vocab, (const float *)logits, ld, (const int64_t *)labels, ignore_index, loss_rows, lse);
-  return hipGetLastError() == hipSuccess ? GPS_OK : GPS_ERR_LAUNCH;
+  return launch_status();
 }
 
 int gps_masked_ce_forward(int n_rows, int vocab, int logits_bf16, const void *logits, long long ld,
@@ -345,7 +338,7 @@ int gps_masked_ce_backward_rows(int n_rows, int vocab, int logits_bf16, const vo
     hipLaunchKernelGGL(gps_loss::masked_ce_bwd_kernel<float>, dim3(n_rows), dim3(gps_loss::kBlock), 0, s, n_rows,
                        vocab, (const float *)logits, ld, (const int64_t *)labels, ignore_index, lse, grad_rows,
                        (float *)dlogits, ldd);
-  return hipGetLastError() == hipSuccess ? GPS_OK : GPS_ERR_LAUNCH;
+  return launch_status();
 }
 
 int gps_masked_ce_backward(int n_rows, int vocab, int logits_bf16, const void *logits, long long ld,
@@ -361,7 +354,7 @@ int gps_lm_row_plan(int n_rows, int vocab, const long long *labels, long long ig
   if (!n_valid || (n_rows > 0 && (!labels || !perm || !labels_out))) return GPS_ERR_INVALID_ARGUMENT;
   hipLaunchKernelGGL(gps_loss::lm_row_plan_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, n_rows, vocab,
                      (const int64_t *)labels, ignore_index, (int64_t *)perm, (int64_t *)labels_out, n_valid);
-  return hipGetLastError() == hipSuccess ? GPS_OK : GPS_ERR_LAUNCH;
+  return launch_status();
 }
 
 }  // extern "C"

@@ -12,11 +12,13 @@
 // launches (x is read once: dx and d att together; then the softmax Jacobian, dh and the per-workgroup partial sums of
 // dw2 / db2, which the last workgroup to arrive adds in a fixed order: no float atomics, run-to-run identical).
 // The BCE loss is one launch per direction, workgroup partials + the same ticket finish.  Memory-bound throughout:
-// 16-byte loads (8 bf16 or 2 x 4 fp32 per thread and trip), fp32 accumulation.
+// 16-byte loads (8 bf16 or 2 x 4 fp32 per thread and trip), fp32 accumulation.  Row access (load8 / store8, bf16 stores
+// by f2bf), wave reductions and the ticket (publish / arrive_and_last / peek) are gps_dev.h's.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "gps_bce_dev.h"
+#include "gps_dev.h"
 #include "gps_hip.h"
 
 namespace gps_qa {
@@ -28,74 +30,7 @@ constexpr int kRowsDh = 32;        // token rows per workgroup of the dh / dw2 k
 constexpr int kMaxG = 4;
 constexpr int kBceMaxBlocks = 1024;
 
-__device__ __forceinline__ float wave_sum(float v) {
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-  for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-  return v;
-}
-__device__ __forceinline__ uint32_t f2bf(float f) {                 // round to nearest even; NaN stays NaN
-  uint32_t u = __float_as_uint(f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return u >> 16;
-}
-// 8 consecutive elements starting at element index `idx` (a multiple of 8 from a 16-byte aligned base)
-template <bool BF16>
-__device__ __forceinline__ void load8(const void *base, size_t idx, float v[8]) {
-  if constexpr (BF16) {
-    const uint4 u = *reinterpret_cast<const uint4 *>(reinterpret_cast<const uint16_t *>(base) + idx);
-    v[0] = __uint_as_float(u.x << 16); v[1] = __uint_as_float(u.x & 0xffff0000u);
-    v[2] = __uint_as_float(u.y << 16); v[3] = __uint_as_float(u.y & 0xffff0000u);
-    v[4] = __uint_as_float(u.z << 16); v[5] = __uint_as_float(u.z & 0xffff0000u);
-    v[6] = __uint_as_float(u.w << 16); v[7] = __uint_as_float(u.w & 0xffff0000u);
-  } else {
-    const float4 *p = reinterpret_cast<const float4 *>(reinterpret_cast<const float *>(base) + idx);
-    const float4 a = p[0], b = p[1];
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-  }
-}
-template <bool BF16>
-__device__ __forceinline__ void store8(void *base, size_t idx, const float v[8]) {
-  if constexpr (BF16) {
-    uint4 u;
-    u.x = f2bf(v[0]) | (f2bf(v[1]) << 16); u.y = f2bf(v[2]) | (f2bf(v[3]) << 16);
-    u.z = f2bf(v[4]) | (f2bf(v[5]) << 16); u.w = f2bf(v[6]) | (f2bf(v[7]) << 16);
-    *reinterpret_cast<uint4 *>(reinterpret_cast<uint16_t *>(base) + idx) = u;
-  } else {
-    float4 *p = reinterpret_cast<float4 *>(reinterpret_cast<float *>(base) + idx);
-    p[0] = make_float4(v[0], v[1], v[2], v[3]);
-    p[1] = make_float4(v[4], v[5], v[6], v[7]);
-  }
-}
-template <bool BF16>
-__device__ __forceinline__ float load1(const void *base, size_t idx) {
-  if constexpr (BF16) return __uint_as_float((uint32_t) reinterpret_cast<const uint16_t *>(base)[idx] << 16);
-  else return reinterpret_cast<const float *>(base)[idx];
-}
-template <bool BF16>
-__device__ __forceinline__ void store1(void *base, size_t idx, float v) {
-  if constexpr (BF16) reinterpret_cast<uint16_t *>(base)[idx] = (uint16_t)f2bf(v);
-  else reinterpret_cast<float *>(base)[idx] = v;
-}
-__device__ __forceinline__ void publish(float *p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ float peek(const float *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-// every thread's publish()ed values are in memory, then thread 0 takes a ticket: true in EVERY thread of the last of
-// `count` workgroups to arrive (`flag` = one int of LDS).  The ticket word is left at zero.
-__device__ __forceinline__ bool arrive_and_last(unsigned int *ticket, unsigned int count, int *flag) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned int t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const bool last = t == count - 1u;
-    if (last) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    *flag = last ? 1 : 0;
-  }
-  __syncthreads();
-  return *flag != 0;
-}
+using namespace gps_dev;
 
 // ---------------------------------------------------------------------------------------------------------------------
 // AttFlat forward.  grid (ceil(D / 128), B), 256 threads.
@@ -433,8 +368,8 @@ __global__ __launch_bounds__(kBlock) void bce_kernel(int rows, int cols, const v
 
 }  // namespace gps_qa
 
-static inline int launch_status() { return hipGetLastError() == hipSuccess ? GPS_OK : GPS_ERR_LAUNCH; }
-static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+using gps_dev::aligned16;
+using gps_dev::launch_status;
 static inline int attflat_shape_status(int B, int T, int G, int D, int M) {
   if (B < 0 || T < 1 || G < 1 || D < 1 || M < 1) return GPS_ERR_INVALID_ARGUMENT;
   if (T > 512 || G > gps_qa::kMaxG || (D & 7) || (M & 7) || D > 2048 || M > 1024) return GPS_ERR_UNSUPPORTED;
@@ -497,7 +432,7 @@ int gps_attflat_backward(int B, int T, int G, int D, int M, int x_bf16, const vo
     else
       hipLaunchKernelGGL(gps_qa::attflat_bwd_x_kernel<false>, grid, dim3(gps_qa::kBlock), lds, (hipStream_t)stream, T, G, D,
                          x, ld_x, att, dpooled, dx, ld_dx, datt);
-    if (hipGetLastError() != hipSuccess) return GPS_ERR_LAUNCH;
+    if (launch_status() != GPS_OK) return GPS_ERR_LAUNCH;
   }
   const int M8 = M >> 3;
   const int RG = gps_qa::kBlock / M8 < gps_qa::kRowsDh ? gps_qa::kBlock / M8 : gps_qa::kRowsDh;

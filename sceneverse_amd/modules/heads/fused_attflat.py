@@ -10,7 +10,6 @@ from typing import Optional
 import torch
 
 from ... import _native
-from ...optim.loss.fused_contra import _ticket
 
 MAX_T, MAX_G, MAX_D, MAX_M = 512, 4, 2048, 1024
 
@@ -84,7 +83,7 @@ class _AttFlatPool(torch.autograd.Function):
                 int(hc.dtype == torch.bfloat16), hc.data_ptr(), w32.data_ptr(),
                 None if keep8 is None else keep8.data_ptr(), att.data_ptr(), dpooled.data_ptr(),
                 None if dx is None else dx.data_ptr(), D, None if dh is None else dh.data_ptr(), dw2.data_ptr(),
-                db2.data_ptr(), ws.data_ptr(), _ticket(dev, "attflat").data_ptr(), torch.cuda.current_stream().cuda_stream)
+                db2.data_ptr(), ws.data_ptr(), _native.ticket(dev, "attflat").data_ptr(), torch.cuda.current_stream().cuda_stream)
         _native.check(st, "attflat_backward")
         w_dtype, b_dtype = ctx.meta
         return (dx, dh, dw2.to(w_dtype) if ctx.needs_input_grad[2] else None,

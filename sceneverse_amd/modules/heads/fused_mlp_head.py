@@ -17,7 +17,6 @@ import torch.nn.functional as F
 from torch import nn
 
 from ... import _native
-from ...optim.loss.fused_contra import _ticket
 
 MIN_D, MAX_D = 8, 1024
 
@@ -124,7 +123,7 @@ def tail_backward(h: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, mean
             None if keep8 is None else keep8.data_ptr(), None if dlogit is None else dlogit.data_ptr(),
             None if dz16 is None else dz16.data_ptr(), dpre.data_ptr(), dpre.stride(0), dgamma.data_ptr(), dbeta.data_ptr(),
             None if dw2 is None else dw2.data_ptr(), None if db2 is None else db2.data_ptr(), partial.data_ptr(),
-            _ticket(dev, "mlp_tail").data_ptr(), torch.cuda.current_stream().cuda_stream)
+            _native.ticket(dev, "mlp_tail").data_ptr(), torch.cuda.current_stream().cuda_stream)
     _native.check(st, "mlp_tail_backward")
     return dpre, dgamma, dbeta, dw2, db2
 

@@ -12,7 +12,7 @@ from typing import Optional
 import torch
 
 from ... import _native
-from .fused_contra import _LDS_LIMIT, _rows_ok, _ticket
+from .fused_contra import _LDS_LIMIT, _rows_ok
 
 
 def bce_logits_usable(x: torch.Tensor, y: torch.Tensor, weight: Optional[torch.Tensor] = None) -> bool:
@@ -41,7 +41,7 @@ class _BCELogitsSum(torch.autograd.Function):
             st = lib.gps_bce_logits_forward(
                 rows, cols, int(x.dtype == torch.bfloat16), x.data_ptr(), x.stride(0), int(y.dtype == torch.float32),
                 y.data_ptr(), None if w8 is None else w8.data_ptr(), float(scale), partial.data_ptr(), loss.data_ptr(),
-                _ticket(dev, "bce_logits").data_ptr(), torch.cuda.current_stream().cuda_stream)
+                _native.ticket(dev, "bce_logits").data_ptr(), torch.cuda.current_stream().cuda_stream)
         _native.check(st, "bce_logits_forward")
         ctx.save_for_backward(x, y, *(() if w8 is None else (w8,)))
         ctx.scale = float(scale)
@@ -95,7 +95,7 @@ class _TextObjBCE(torch.autograd.Function):
             st = _native.load().gps_text_obj_bce_forward(
                 B, O, D, obj.data_ptr(), text.data_ptr(), labels.data_ptr(), masks.data_ptr(), float(eps),
                 cosv.data_ptr(), coef.data_ptr(), inv_o.data_ptr(), inv_t.data_ptr(), loss_rows.data_ptr(), scal.data_ptr(),
-                _ticket(dev, "text_obj_bce").data_ptr(), torch.cuda.current_stream().cuda_stream)
+                _native.ticket(dev, "text_obj_bce").data_ptr(), torch.cuda.current_stream().cuda_stream)
         _native.check(st, "text_obj_bce_forward")
         ctx.save_for_backward(obj, text, cosv, coef, inv_o, inv_t, scal)
         ctx.eps = float(eps)

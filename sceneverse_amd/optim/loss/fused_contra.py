@@ -10,18 +10,6 @@ import torch
 
 from ... import _native
 
-_TICKETS = {}
-
-
-def _ticket(device: torch.device, site: str) -> torch.Tensor:
-    """One zeroed arrival counter per device and call site (the kernels leave it at zero)."""
-    key = (device.index if device.index is not None else torch.cuda.current_device(), site)
-    t = _TICKETS.get(key)
-    if t is None:
-        t = _TICKETS[key] = torch.zeros(1, dtype=torch.int32, device=device)
-    return t
-
-
 def _rows_ok(*ts) -> bool:
     return all(t.is_cuda and t.dtype == torch.float32 and t.shape[-1] % 4 == 0 and t.shape[-1] <= 8192 for t in ts)
 
@@ -41,7 +29,7 @@ class _TextObjCE(torch.autograd.Function):
             st = _native.load().gps_text_obj_ce_forward(
                 B, O, D, obj.data_ptr(), text.data_ptr(), labels.data_ptr(), masks.data_ptr(), float(eps), int(ignore_index),
                 cosv.data_ptr(), prob.data_ptr(), inv_o.data_ptr(), inv_t.data_ptr(), loss_rows.data_ptr(), scal.data_ptr(),
-                _ticket(dev, "text_obj").data_ptr(), torch.cuda.current_stream().cuda_stream)
+                _native.ticket(dev, "text_obj").data_ptr(), torch.cuda.current_stream().cuda_stream)
         _native.check(st, "text_obj_ce_forward")
         ctx.save_for_backward(obj, text, labels, cosv, prob, inv_o, inv_t, scal)
         ctx.meta = (float(eps), int(ignore_index))
@@ -94,7 +82,7 @@ class _ClipLoss(torch.autograd.Function):
             st = _native.load().gps_clip_loss_forward(
                 n, D, int(bool(normalize)), a.data_ptr(), b.data_ptr(), scale32.data_ptr(), float(max_scale), float(eps),
                 M.data_ptr(), lse_row.data_ptr(), lse_col.data_ptr(), inv_a.data_ptr(), inv_b.data_ptr(), rows.data_ptr(),
-                loss.data_ptr(), _ticket(dev, "clip_fwd").data_ptr(), torch.cuda.current_stream().cuda_stream)
+                loss.data_ptr(), _native.ticket(dev, "clip_fwd").data_ptr(), torch.cuda.current_stream().cuda_stream)
         _native.check(st, "clip_loss_forward")
         ctx.save_for_backward(a, b, scale32, M, lse_row, lse_col, inv_a, inv_b)
         ctx.meta = (bool(normalize), float(max_scale), float(eps), scale.dtype, scale.shape)
@@ -116,7 +104,7 @@ class _ClipLoss(torch.autograd.Function):
                 n, D, int(normalize), a.data_ptr(), b.data_ptr(), scale32.data_ptr(), max_scale, eps, M.data_ptr(),
                 lse_row.data_ptr(), lse_col.data_ptr(), inv_a.data_ptr(), inv_b.data_ptr(), g.data_ptr(),
                 da.data_ptr() if feats else None, db.data_ptr() if feats else None, dscale.data_ptr(), rows.data_ptr(),
-                _ticket(a.device, "clip_bwd").data_ptr(), torch.cuda.current_stream().cuda_stream)
+                _native.ticket(a.device, "clip_bwd").data_ptr(), torch.cuda.current_stream().cuda_stream)
         _native.check(st, "clip_loss_backward")
         ds = dscale.reshape(s_shape).to(s_dtype) if ctx.needs_input_grad[2] else None
         return (da if ctx.needs_input_grad[0] else None), (db if ctx.needs_input_grad[1] else None), ds, None, None, None

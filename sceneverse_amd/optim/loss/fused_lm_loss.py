@@ -30,18 +30,6 @@ import torch
 from ... import _native
 from ...modules.layers import gemm as G
 
-_TICKETS = {}
-
-
-def _ticket(device: torch.device) -> torch.Tensor:
-    """The zeroed arrival counter of gps_masked_ce_forward_rows' mean (left at zero by every launch)."""
-    key = device.index if device.index is not None else torch.cuda.current_device()
-    t = _TICKETS.get(key)
-    if t is None:
-        t = _TICKETS[key] = torch.zeros(1, dtype=torch.int32, device=device)
-    return t
-
-
 class HitsSink:
     """Where `_SparseLMLoss.forward` adds its hit counts: `words` = 6 int64 counter words of gps_cls_hits (hits and
     labelled rows in the first two); `launches` counts the forward passes that have added to them.  With `keep` set the
@@ -168,7 +156,7 @@ class _SparseLMLoss(torch.autograd.Function):
         with torch.cuda.device(dev):
             st = lib.gps_masked_ce_forward_rows(n, V, 1, logits.data_ptr(), Vp, lp.data_ptr(), int(ignore_index),
                                                 n_valid.data_ptr(), rows.data_ptr(), lse.data_ptr(), mean.data_ptr(),
-                                                _ticket(dev).data_ptr(), torch.cuda.current_stream().cuda_stream)
+                                                _native.ticket(dev, "lm_loss").data_ptr(), torch.cuda.current_stream().cuda_stream)
         _native.check(st, "masked_ce_forward")
         sink = _HITS_SINK
         if sink is not None:

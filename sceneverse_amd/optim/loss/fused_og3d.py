@@ -9,7 +9,6 @@ from __future__ import annotations
 import torch
 
 from ... import _native
-from .fused_contra import _ticket
 
 MAX_O = 512
 
@@ -36,7 +35,7 @@ class _Og3dCE(torch.autograd.Function):
         from ...pointnet2._ext import _timed
         with torch.cuda.device(dev), _timed(f"og3d_ce_forward(B={B},O={O})", 8 * B * O + 8 * B):
             st = lib.gps_og3d_ce_forward(B, O, x.data_ptr(), x.stride(0) if B > 1 else O, tgt.data_ptr(), loss.data_ptr(),
-                                         unit.data_ptr(), partial.data_ptr(), _ticket(dev, "og3d_ce").data_ptr(),
+                                         unit.data_ptr(), partial.data_ptr(), _native.ticket(dev, "og3d_ce").data_ptr(),
                                          torch.cuda.current_stream().cuda_stream)
         _native.check(st, "og3d_ce_forward")
         ctx.save_for_backward(unit)

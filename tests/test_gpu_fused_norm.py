@@ -5,12 +5,18 @@ bf16 h (autocast flow: fp32 residual stream + bf16 branch) and bf16 x: same boun
 reference fed the same rounded inputs; bf16 outputs/gradients add one 2^-8 rounding.
 Dropout: the keep mask is a deterministic function of (device seed word, element), identical in
 forward and backward, with keep rate 1 - p."""
+import os
+import sys
+
 import pytest
 import torch
 import torch.nn.functional as F
 from torch import nn
 
 from sceneverse_amd.modules.layers.fused_norm import _AddDropoutLN, add_dropout_layer_norm
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
+import make_golden_ln_reduce as ln_digests  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -126,6 +132,29 @@ def test_partial_row_reduction_is_exact_order_independent_and_reusable(parts, d)
     plain = torch.empty((2, d), device=DEV)
     _native.check(lib.gps_ln_reduce_partials(parts, d, part.data_ptr(), plain.data_ptr(), None, stream), "reduce")
     assert (plain.double() - ref).abs().max().item() <= 1e-5 * max(1.0, ref.abs().max().item())
+
+
+def test_frozen_reduction_digests_cover_every_case():
+    assert sorted(ln_digests.load()) == sorted(ln_digests.keys())
+
+
+@pytest.mark.parametrize("parts,d", [(p, d) for d in ln_digests.DS for p in ln_digests.PARTS])
+def test_partial_row_reduction_bits_are_the_frozen_ones(parts, d):
+    """tests/golden/ln_reduce_digests.json (tests/golden/make_golden_ln_reduce.py): SHA-256 of the raw output of
+    gps_ln_reduce_partials (with and without scratch) and of gps_ln_reduce_partials_grouped (stored over / added to a
+    preset buffer), recorded from the two kernels as they were before they shared one device body.  The summation order is
+    fixed, so a mismatch is a change of arithmetic, never a tolerance.  The grouped form stores the bits of the single
+    form with scratch, and every ticket word is zero again after a launch."""
+    frozen = ln_digests.load()
+    outs = {}
+    for form in ln_digests.FORMS:
+        out, tickets = ln_digests.compute(form, parts, d)
+        got = ln_digests.sha(out)
+        print(form, parts, d, got)
+        assert got == frozen[ln_digests.key(form, parts, d)], form
+        assert tickets is None or int(tickets.abs().sum()) == 0, form
+        outs[form] = out
+    assert torch.equal(outs["grouped/acc=0"], outs["single/scratch"])
 
 
 @pytest.mark.parametrize("shape", [(64, 80, 768), (64, 768), (3, 1, 100), (5, 2048)])
