@@ -94,6 +94,23 @@ EPI_BIAS_GELU_FACTOR, EPI_MUL_AUX = 8, 9
 NON_STATUS_RESTYPES = {"gps_embedding_grad_scratch_ints": ctypes.c_longlong, "gps_point_set_object_extent": None,
                        "gps_attflat_backward_ws_floats": ctypes.c_longlong}
 
+# entries outside SIGNATURES (sizes, settings and diagnostics: none of them launches): name -> (argtypes, restype)
+OTHER_SIGNATURES = {
+    "gps_abi_version": ([], _i),
+    "gps_error_string": ([_i], ctypes.c_char_p),
+    "gps_last_hip_error": ([], ctypes.c_char_p),
+    "gps_sa_mlp_wpack_floats": ([_i, _i, _i, _i], ctypes.c_longlong),
+    "gps_sa_mlp_layer_floats": ([_i, _i], ctypes.c_longlong),
+    "gps_sa_mlp_layer_floats_bf16x3": ([_i, _i], ctypes.c_longlong),
+    "gps_gemm_workspace_floats": ([_i, _i, _i, _i], ctypes.c_longlong),
+    "gps_gemm_sk_workspace_bytes": ([], ctypes.c_longlong),
+    "gps_adamw_chunk_elems": ([], _i),
+    "gps_attn_set_stream_min_tiles": ([_i, _i], None),
+    "gps_ln_partial_rows": ([_i], _i),
+    "gps_ln_reduce_scratch_bytes": ([_i], ctypes.c_longlong),
+    "gps_ln_reduce_grouped_scratch_bytes": ([_i], ctypes.c_longlong),
+}
+
 # name -> argtypes, mirroring include/gps_hip.h one to one
 SIGNATURES = {
     "gps_adamw_step": [_i, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp],
@@ -229,38 +246,14 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
     if not os.path.exists(LIB_PATH):
         raise GpsNativeError(f"{LIB_PATH} not found; run `python -c 'import __graft_entry__ as g; g.build()'`")
     lib = ctypes.CDLL(LIB_PATH)
-    lib.gps_abi_version.restype = _i
-    lib.gps_error_string.restype = ctypes.c_char_p
-    lib.gps_error_string.argtypes = [_i]
-    lib.gps_last_hip_error.restype = ctypes.c_char_p
-    lib.gps_sa_mlp_wpack_floats.restype = ctypes.c_longlong
-    lib.gps_sa_mlp_wpack_floats.argtypes = [_i, _i, _i, _i]
-    lib.gps_sa_mlp_layer_floats.restype = ctypes.c_longlong
-    lib.gps_sa_mlp_layer_floats.argtypes = [_i, _i]
-    lib.gps_sa_mlp_layer_floats_bf16x3.restype = ctypes.c_longlong
-    lib.gps_sa_mlp_layer_floats_bf16x3.argtypes = [_i, _i]
-    lib.gps_gemm_workspace_floats.restype = ctypes.c_longlong
-    lib.gps_gemm_workspace_floats.argtypes = [_i, _i, _i, _i]
-    lib.gps_adamw_chunk_elems.restype = _i
-    lib.gps_adamw_chunk_elems.argtypes = []
-    lib.gps_attn_set_stream_min_tiles.restype = None
-    lib.gps_attn_set_stream_min_tiles.argtypes = [_i, _i]
-    lib.gps_ln_partial_rows.restype = _i
-    lib.gps_ln_partial_rows.argtypes = [_i]
-    lib.gps_ln_reduce_scratch_bytes.restype = ctypes.c_longlong
-    lib.gps_ln_reduce_scratch_bytes.argtypes = [_i]
-    lib.gps_ln_reduce_grouped_scratch_bytes.restype = ctypes.c_longlong
-    lib.gps_ln_reduce_grouped_scratch_bytes.argtypes = [_i]
+    # an entry of SIGNATURES returns an `int` status unless NON_STATUS_RESTYPES names its type (a 64-bit scratch size read
+    # as c_int under-allocates for large n * d)
     for name, argtypes in SIGNATURES.items():
         fn = getattr(lib, name)
-        fn.argtypes = argtypes
-        fn.restype = _i
-    # the entries of SIGNATURES that do NOT return a status (set after the loop above, which would overwrite them:
-    # a 64-bit scratch size read as c_int under-allocates for large n * d)
-    for name, restype in NON_STATUS_RESTYPES.items():
-        getattr(lib, name).restype = restype
-    lib.gps_gemm_sk_workspace_bytes.restype = ctypes.c_longlong
-    lib.gps_gemm_sk_workspace_bytes.argtypes = []
+        fn.argtypes, fn.restype = argtypes, NON_STATUS_RESTYPES.get(name, _i)
+    for name, (argtypes, restype) in OTHER_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.argtypes, fn.restype = argtypes, restype
     _lib = lib
     return lib
 

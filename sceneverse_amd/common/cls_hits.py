@@ -8,7 +8,8 @@ from typing import Optional
 
 import torch
 
-from .. import _native
+from .. import _launch, _native
+from .._launch import ptr
 
 WORDS = 6                         # hits, count, hits & a, count & a, hits & b, count & b
 
@@ -72,7 +73,6 @@ def problem(logits: torch.Tensor, labels: torch.Tensor, counters: torch.Tensor, 
             raise ValueError("cls_hits: labels, masks, extent and counters must live on the logits' GPU")
     if rows_dev is not None and (rows_dev.dtype != torch.int32 or rows_dev.numel() != 1):
         raise ValueError("cls_hits: rows_dev must be one int32 word")
-    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
     p = _native.ClsHitsProblem(
         rows=rows, cols=cols, logits=x.data_ptr(), ld=x.stride(0) if rows > 1 else V,
         logits_bf16=int(x.dtype == torch.bfloat16), use_ignore=int(ignore_index is not None),
@@ -89,15 +89,12 @@ def launch(problems, device: torch.device) -> None:
     if len(problems) > _native.CLS_HITS_MAX_PROBLEMS:
         raise ValueError(f"cls_hits: {len(problems)} problems in one launch (at most {_native.CLS_HITS_MAX_PROBLEMS})")
     arr = (_native.ClsHitsProblem * len(problems))(*[p for p, _ in problems])
-    with torch.cuda.device(device):
-        st = _native.load().gps_cls_hits(arr, len(problems), torch.cuda.current_stream(device).cuda_stream)
-    _native.check(st, "cls_hits")
+    _launch.launch("gps_cls_hits", arr, len(problems), device=device)
 
 
 def term(hits: torch.Tensor, count: Optional[torch.Tensor] = None, sub_hits: Optional[torch.Tensor] = None,
          sub_count: Optional[torch.Tensor] = None, eps: float = 0.0, const_denominator: Optional[float] = None):
     """One gps_metric_term over 1-element views of the counter words."""
-    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
     return _native.MetricTerm(hits=ptr(hits), count=ptr(count), sub_hits=ptr(sub_hits), sub_count=ptr(sub_count),
                               eps=float(eps), const_denominator=float(const_denominator or 0.0),
                               use_const_denominator=int(const_denominator is not None), reserved=0)
@@ -109,9 +106,5 @@ def fold(terms, weight: float, n_mean: int, last: torch.Tensor, acc: torch.Tenso
         if t.dtype != torch.float64 or t.numel() < n or not t.is_contiguous() or t.device.type != "cuda":
             raise ValueError("metrics_fold: last / acc / total must be contiguous float64 GPU tensors")
     arr = (_native.MetricTerm * max(len(terms), 1))(*terms)
-    dev = last.device
-    with torch.cuda.device(dev):
-        st = _native.load().gps_metrics_fold(len(terms), arr, ctypes.c_double(float(weight)), int(n_mean),
-                                             last.data_ptr(), acc.data_ptr(), total.data_ptr(),
-                                             torch.cuda.current_stream(dev).cuda_stream)
-    _native.check(st, "metrics_fold")
+    _launch.launch("gps_metrics_fold", len(terms), arr, ctypes.c_double(float(weight)), int(n_mean), last, acc, total,
+                   device=last.device)

@@ -27,7 +27,7 @@ from typing import Dict, List, Mapping, Optional, Sequence
 import numpy as np
 import torch
 
-from .. import _native
+from .._launch import launch
 
 
 class PackedScans:
@@ -198,26 +198,16 @@ def obj_processing_post(packed: PackedScans, row_obj: torch.Tensor, num_points: 
         locs = torch.empty((B, O, 6), dtype=torch.float32, device=dev)
         masks = torch.empty((B, O), dtype=torch.uint8, device=dev)
     boxes = torch.empty((B, O, 6), dtype=torch.float32, device=dev) if need_boxes else None
-    rot_ptr = row_rot_ptr = None
-    keep = []
+    rot_t = row_rot = None
     if rot is not None:
         rot_t, row_rot = rot_rows(rot, B, O, dev)
-        keep = [rot_t, row_rot]
-        rot_ptr, row_rot_ptr = rot_t.data_ptr(), row_rot.data_ptr()
     if sample_idx is not None:
         sample_idx = sample_idx.to(device=dev, dtype=torch.int32).contiguous()
         assert sample_idx.shape == (B, O, num_points), sample_idx.shape
-    from ..pointnet2._ext import _timed
-    with torch.cuda.device(dev), _timed(f"obj_processing_post(rows={n_rows},P={num_points})", nbytes):
-        st = _native.load().gps_obj_processing_post(
-            n_rows, num_points, packed.xyz.data_ptr(), packed.rgb.data_ptr() if packed.rgb is not None else None,
-            int(packed.rgb is None or packed.rgb.dtype == torch.uint8),
-            packed.obj_offsets.data_ptr(), row_obj.data_ptr(),
-            sample_idx.data_ptr() if sample_idx is not None else None, int(seed) & ((1 << 64) - 1),
-            rot_ptr, row_rot_ptr, fts.data_ptr(), locs.data_ptr(), boxes.data_ptr() if need_boxes else None,
-            masks.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-    _native.check(st, "obj_processing_post")
-    del keep
+    launch("gps_obj_processing_post", n_rows, num_points, packed.xyz, packed.rgb,
+           int(packed.rgb is None or packed.rgb.dtype == torch.uint8), packed.obj_offsets, row_obj, sample_idx,
+           int(seed) & ((1 << 64) - 1), rot_t, row_rot, fts, locs, boxes, masks, device=dev,
+           label=f"obj_processing_post(rows={n_rows},P={num_points})", nbytes=nbytes, what="obj_processing_post")
     res = {"obj_fts": fts, "obj_locs": locs, "obj_masks": masks if masks.dtype == torch.bool else masks.bool()}
     if need_boxes:
         res["obj_boxes"] = boxes
@@ -263,11 +253,8 @@ def obj_boxes(packed: PackedScans) -> torch.Tensor:
         return boxes
     work = torch.from_numpy(boxes_work_list(packed.sizes_host)).to(dev)
     ws = torch.empty(n * 6, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        st = _native.load().gps_obj_boxes(n, int(packed.xyz.shape[0]), int(work.shape[0]), packed.xyz.data_ptr(),
-                                          int(packed.rgb is None), work.data_ptr(), ws.data_ptr(), boxes.data_ptr(),
-                                          torch.cuda.current_stream(dev).cuda_stream)
-    _native.check(st, "obj_boxes")
+    launch("gps_obj_boxes", n, int(packed.xyz.shape[0]), int(work.shape[0]), packed.xyz, int(packed.rgb is None), work, ws, boxes,
+           device=dev)
     return boxes
 
 
@@ -313,13 +300,8 @@ def refer_targets(packed: PackedScans, row_obj: torch.Tensor, tgt_obj, scan_ids:
             raise ValueError("refer_targets: `out` tensors must be contiguous int64 (B,O) / (B,1) on the scans' GPU")
     else:
         res = {name: torch.empty(shapes[name], dtype=torch.int64, device=dev) for name, _ in _REFER_OUT}
-    with torch.cuda.device(dev):
-        st = _native.load().gps_refer_targets(
-            B, O, packed.n_objects, int(pc_type == "gt"), packed.boxes.data_ptr(), packed.labels.data_ptr(),
-            row_obj.data_ptr(), tgt.data_ptr(), ranges.data_ptr(), res["tgt_object_id_iou25"].data_ptr(),
-            res["tgt_object_id_iou50"].data_ptr(), res["tgt_object_id"].data_ptr(), res["obj_labels"].data_ptr(),
-            torch.cuda.current_stream(dev).cuda_stream)
-    _native.check(st, "refer_targets")
+    launch("gps_refer_targets", B, O, packed.n_objects, int(pc_type == "gt"), packed.boxes, packed.labels, row_obj, tgt, ranges,
+           res["tgt_object_id_iou25"], res["tgt_object_id_iou50"], res["tgt_object_id"], res["obj_labels"], device=dev)
     return res
 
 
@@ -458,20 +440,11 @@ def obj_processing_aug(packed: PackedScans, row_obj: torch.Tensor, num_points: i
             raise ValueError("obj_processing_aug: jitter_noise must be float32 or float64")
         jitter_noise = jitter_noise.to(device=dev).contiguous()
         assert jitter_noise.shape == (B, O, num_points, 3), jitter_noise.shape
-    from ..pointnet2._ext import _timed
-    with torch.cuda.device(dev), _timed(f"obj_processing_aug(rows={n_rows},P={num_points})", nbytes):
-        st = _native.load().gps_obj_processing_aug(
-            n_rows, num_points, packed.xyz.data_ptr(), packed.rgb.data_ptr() if packed.rgb is not None else None,
-            int(packed.rgb is None or packed.rgb.dtype == torch.uint8),
-            packed.obj_offsets.data_ptr(), row_obj.data_ptr(),
-            sample_idx.data_ptr() if sample_idx is not None else None,
-            jitter_noise.data_ptr() if jitter_noise is not None else None,
-            int(jitter_noise is not None and jitter_noise.dtype == torch.float64), int(seed) & ((1 << 64) - 1),
-            tab.data_ptr() if tab is not None else None, row_aug.data_ptr() if tab is not None else None,
-            tab.shape[0] if tab is not None else 0,
-            fts.data_ptr(), locs.data_ptr(), boxes.data_ptr() if need_boxes else None,
-            masks.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-    _native.check(st, "obj_processing_aug")
+    launch("gps_obj_processing_aug", n_rows, num_points, packed.xyz, packed.rgb,
+           int(packed.rgb is None or packed.rgb.dtype == torch.uint8), packed.obj_offsets, row_obj, sample_idx, jitter_noise,
+           int(jitter_noise is not None and jitter_noise.dtype == torch.float64), int(seed) & ((1 << 64) - 1),
+           tab, row_aug, tab.shape[0] if tab is not None else 0, fts, locs, boxes, masks,
+           device=dev, label=f"obj_processing_aug(rows={n_rows},P={num_points})", nbytes=nbytes, what="obj_processing_aug")
     res = {"obj_fts": fts, "obj_locs": locs, "obj_masks": masks if masks.dtype == torch.bool else masks.bool()}
     if need_boxes:
         res["obj_boxes"] = boxes

@@ -50,6 +50,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from ._launch import launch
 from .common import dist_utils
 
 _CAPTURE_MODE = "thread_local"     # split-graph data-parallel captures (see _graph_dp_step)
@@ -808,7 +809,6 @@ class ScanReferCounter:
         self.counts.zero_()
 
     def update(self, og3d_logits: torch.Tensor, batch: dict) -> None:
-        from . import _native
         dev = self.counts.device
         if og3d_logits.device.type != "cuda" or dev.type != "cuda":
             raise RuntimeError("ScanReferCounter runs on libgps_hip.so: logits and counters must live on a GPU (no CPU path)")
@@ -828,12 +828,8 @@ class ScanReferCounter:
                 raise ValueError(f"ScanReferCounter: {name} must be contiguous {dtype} {shape} on the logits' GPU")
         if og3d_logits.device != dev:
             raise ValueError("ScanReferCounter: the logits live on another GPU than the counters")
-        with torch.cuda.device(dev):
-            st = _native.load().gps_refer_metrics(
-                B, O, og3d_logits.data_ptr(), og3d_logits.stride(0) if B > 1 else O,
-                int(og3d_logits.dtype == torch.bfloat16), iou25.data_ptr(), iou50.data_ptr(), tgt.data_ptr(),
-                mult.data_ptr(), self.counts.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-        _native.check(st, "refer_metrics")
+        launch("gps_refer_metrics", B, O, og3d_logits, og3d_logits.stride(0) if B > 1 else O,
+               int(og3d_logits.dtype == torch.bfloat16), iou25, iou50, tgt, mult, self.counts, device=dev)
 
     def result(self, include_count: bool = False) -> dict:
         """The reference's keys; ratios hits / max(count, 1), or with include_count the (hits, count) pairs."""

@@ -12,6 +12,7 @@ type embeddings are read straight from the embedding table on whatever device th
 import torch
 import torch.nn as nn
 
+from ..._launch import launch
 from ..build import GROUNDING_REGISTRY
 from ..layers.transformers import (TransformerDecoderLayer, TransformerEncoderLayer,
                                    TransformerSpatialDecoderLayer)
@@ -94,12 +95,6 @@ class UnifiedSpatialCrossEncoderV1(nn.Module):
         return txt_embeds, obj_embeds
 
 
-def _rows_call(name, *args):
-    from ... import _native
-    st = getattr(_native.load(), name)(*args, torch.cuda.current_stream().cuda_stream)
-    _native.check(st, name)
-
-
 class _JointEmbed(torch.autograd.Function):
     """The packed input of the first joint layer from the text rows a (B, La, D), the object rows b (B, Lb, D) and their
     per-layer addends ea, eb (token-type / location embeddings): x = joint + extra, e = extra, x16 = bf16(x), row r = flat row
@@ -116,9 +111,8 @@ class _JointEmbed(torch.autograd.Function):
         x = torch.empty((n, D), dtype=torch.float32, device=a.device)
         e = torch.empty((n, D), dtype=torch.float32, device=a.device)
         x16 = torch.empty((n, D), dtype=torch.bfloat16, device=a.device)
-        with torch.cuda.device(a.device):
-            _rows_call("gps_joint_embed_forward", B, La, Lb, D, a.data_ptr(), b.data_ptr(), ea.data_ptr(), eb.data_ptr(),
-                       perm.data_ptr(), n_live.data_ptr(), x.data_ptr(), e.data_ptr(), x16.data_ptr())
+        launch("gps_joint_embed_forward", B, La, Lb, D, a, b, ea, eb, perm, n_live, x, e, x16, device=a.device,
+               what="gps_joint_embed_forward")
         ctx.save_for_backward(inv, valid8)
         ctx.dims = (B, La, Lb, D)
         return x, e, x16
@@ -132,10 +126,8 @@ class _JointEmbed(torch.autograd.Function):
         de = None if de is None else de.float().contiguous()
         dx16 = None if dx16 is None else dx16.to(torch.bfloat16).contiguous()
         outs = [torch.empty((B, L, D), dtype=torch.float32, device=dev) for L in (La, Lb, La, Lb)]
-        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        with torch.cuda.device(dev):
-            _rows_call("gps_joint_embed_backward", B, La, Lb, D, ptr(dx), ptr(dx16), ptr(de), inv.data_ptr(), valid8.data_ptr(),
-                       *(t.data_ptr() for t in outs))
+        launch("gps_joint_embed_backward", B, La, Lb, D, dx, dx16, de, inv, valid8, *outs, device=dev,
+               what="gps_joint_embed_backward")
         return outs[0], outs[1], outs[2], outs[3], None, None, None, None
 
 
@@ -149,8 +141,7 @@ class _UnpackJoint(torch.autograd.Function):
         x = x.float().contiguous()
         a = torch.empty((B, La, D), dtype=torch.float32, device=x.device)
         b = torch.empty((B, Lb, D), dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            _rows_call("gps_rows_unpack2", B, La, Lb, D, x.data_ptr(), inv.data_ptr(), valid8.data_ptr(), a.data_ptr(), b.data_ptr())
+        launch("gps_rows_unpack2", B, La, Lb, D, x, inv, valid8, a, b, device=x.device, what="gps_rows_unpack2")
         ctx.save_for_backward(perm, n_live)
         ctx.dims = (B, La, Lb, D)
         return a, b
@@ -163,9 +154,7 @@ class _UnpackJoint(torch.autograd.Function):
         da = torch.zeros((B, La, D), dtype=torch.float32, device=dev) if da is None else da.float().contiguous()
         db = torch.zeros((B, Lb, D), dtype=torch.float32, device=dev) if db is None else db.float().contiguous()
         dx = torch.empty((B * (La + Lb), D), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _rows_call("gps_rows_pack2", B, La, Lb, D, da.data_ptr(), db.data_ptr(), perm.data_ptr(), n_live.data_ptr(),
-                       dx.data_ptr(), None)
+        launch("gps_rows_pack2", B, La, Lb, D, da, db, perm, n_live, dx, None, device=dev, what="gps_rows_pack2")
         return dx, None, None, None, None, None, None, None
 
 
@@ -204,7 +193,6 @@ class UnifiedSpatialCrossEncoderV2(nn.Module):
         residual LayerNorms) stop at the device-side row count, attention is the variable-length core, and the result goes
         back into the (B, T, D) layout with ZEROS at the padded positions (the reference leaves unspecified values there).
         At the bench workload 60 % of the 8 320 joint rows are valid."""
-        from ... import _native
         from ..layers import gemm
         from ..layers.fused_attention import fused_varlen_self_attention
         from ..layers.fused_norm import add_dropout_layer_norm
@@ -219,10 +207,7 @@ class UnifiedSpatialCrossEncoderV2(nn.Module):
         i64 = torch.empty(2 * n, dtype=torch.int64, device=dev)
         i32 = torch.empty(B + 2, dtype=torch.int32, device=dev)
         perm, inv, cu, n_live = i64[:n], i64[n:], i32[:B + 1], i32[B + 1:]
-        with torch.cuda.device(dev):
-            st = _native.load().gps_rows_plan(B, T, valid.view(torch.uint8).data_ptr(), perm.data_ptr(), inv.data_ptr(),
-                                              cu.data_ptr(), n_live.data_ptr(), torch.cuda.current_stream().cuda_stream)
-        _native.check(st, "rows_plan")
+        launch("gps_rows_plan", B, T, valid.view(torch.uint8), perm, inv, cu, n_live, device=dev)
         # packed rows straight from the two parts (no concatenated (B, T, D) tensor, no gather of one): zeros in the dead rows,
         # whose (undefined) gradients the reverse launch never reads
         valid8 = valid.view(torch.uint8)

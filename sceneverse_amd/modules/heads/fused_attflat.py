@@ -10,6 +10,7 @@ from typing import Optional
 import torch
 
 from ... import _native
+from ..._launch import launch
 
 MAX_T, MAX_G, MAX_D, MAX_M = 512, 4, 2048, 1024
 
@@ -46,15 +47,10 @@ class _AttFlatPool(torch.autograd.Function):
         dev = x.device
         pooled = torch.empty((B, G * D), dtype=torch.float32, device=dev)
         att = torch.empty((B, T, G), dtype=torch.float32, device=dev)
-        from ...pointnet2._ext import _timed
         nbytes = xr.numel() * xr.element_size() + hc.numel() * hc.element_size() + 4 * (pooled.numel() + att.numel())
-        with torch.cuda.device(dev), _timed(f"attflat_forward(B={B},T={T},G={G},D={D},M={M})", nbytes):
-            st = _native.load().gps_attflat_forward(
-                B, T, G, D, M, int(xr.dtype == torch.bfloat16), xr.data_ptr(), xr.stride(1),
-                int(hc.dtype == torch.bfloat16), hc.data_ptr(), w32.data_ptr(), b32.data_ptr(),
-                None if keep8 is None else keep8.data_ptr(), pooled.data_ptr(), att.data_ptr(),
-                torch.cuda.current_stream().cuda_stream)
-        _native.check(st, "attflat_forward")
+        launch("gps_attflat_forward", B, T, G, D, M, int(xr.dtype == torch.bfloat16), xr, xr.stride(1),
+               int(hc.dtype == torch.bfloat16), hc, w32, b32, keep8, pooled, att, device=dev,
+               label=f"attflat_forward(B={B},T={T},G={G},D={D},M={M})", nbytes=nbytes, what="attflat_forward")
         ctx.save_for_backward(xr, hc, w32, att, *(() if keep8 is None else (keep8,)))
         ctx.meta = (w2.dtype, b2.dtype)
         ctx.mark_non_differentiable(att)
@@ -72,19 +68,13 @@ class _AttFlatPool(torch.autograd.Function):
         dh = torch.empty_like(hc) if ctx.needs_input_grad[1] else None
         dw2 = torch.empty((G, M), dtype=torch.float32, device=dev)
         db2 = torch.empty(G, dtype=torch.float32, device=dev)
-        lib = _native.load()
-        ws = torch.empty(int(lib.gps_attflat_backward_ws_floats(B, T, G, M)), dtype=torch.float32, device=dev)
-        from ...pointnet2._ext import _timed
+        ws = torch.empty(int(_native.load().gps_attflat_backward_ws_floats(B, T, G, M)), dtype=torch.float32, device=dev)
         nbytes = (xr.numel() * xr.element_size() * (2 if dx is not None else 1)
                   + hc.numel() * hc.element_size() * (2 if dh is not None else 1) + 4 * ws.numel())
-        with torch.cuda.device(dev), _timed(f"attflat_backward(B={B},T={T},G={G},D={D},M={M})", nbytes):
-            st = lib.gps_attflat_backward(
-                B, T, G, D, M, int(xr.dtype == torch.bfloat16), xr.data_ptr(), xr.stride(1),
-                int(hc.dtype == torch.bfloat16), hc.data_ptr(), w32.data_ptr(),
-                None if keep8 is None else keep8.data_ptr(), att.data_ptr(), dpooled.data_ptr(),
-                None if dx is None else dx.data_ptr(), D, None if dh is None else dh.data_ptr(), dw2.data_ptr(),
-                db2.data_ptr(), ws.data_ptr(), _native.ticket(dev, "attflat").data_ptr(), torch.cuda.current_stream().cuda_stream)
-        _native.check(st, "attflat_backward")
+        launch("gps_attflat_backward", B, T, G, D, M, int(xr.dtype == torch.bfloat16), xr, xr.stride(1),
+               int(hc.dtype == torch.bfloat16), hc, w32, keep8, att, dpooled, dx, D, dh, dw2, db2, ws,
+               _native.ticket(dev, "attflat"), device=dev, label=f"attflat_backward(B={B},T={T},G={G},D={D},M={M})",
+               nbytes=nbytes, what="attflat_backward")
         w_dtype, b_dtype = ctx.meta
         return (dx, dh, dw2.to(w_dtype) if ctx.needs_input_grad[2] else None,
                 db2.to(b_dtype) if ctx.needs_input_grad[3] else None, None)

@@ -17,6 +17,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from ... import _native
+from ..._launch import launch
 
 MIN_D, MAX_D = 8, 1024
 
@@ -68,7 +69,7 @@ def _vec16(t: torch.Tensor) -> torch.Tensor:
 
 
 def _seed_args(p, seed, seed_dev):
-    return float(p), int(seed) & ((1 << 64) - 1), None if seed_dev is None else seed_dev.data_ptr()
+    return float(p), int(seed) & ((1 << 64) - 1), seed_dev
 
 
 def tail_forward(h: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, p: float = 0.0, seed: int = 0,
@@ -83,16 +84,10 @@ def tail_forward(h: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: 
     logit = torch.empty(n, dtype=torch.float32, device=dev) if w2 is not None else None
     mean = torch.empty(n, dtype=torch.float32, device=dev)
     rstd = torch.empty(n, dtype=torch.float32, device=dev)
-    from ...pointnet2._ext import _timed
-    nbytes = n * d * (h.element_size() + (2 if want_z16 else 0)) + 12 * n
-    with torch.cuda.device(dev), _timed(f"mlp_tail_forward(rows={n},d={d})", nbytes):
-        st = _native.load().gps_mlp_tail_forward(
-            n, d, int(h.dtype == torch.bfloat16), h.data_ptr(), h.stride(0), gamma.data_ptr(), beta.data_ptr(), float(eps),
-            *_seed_args(p, seed, seed_dev), None if w2 is None else w2.data_ptr(), None if b2 is None else b2.data_ptr(),
-            None if keep8 is None else keep8.data_ptr(), None if z16 is None else z16.data_ptr(),
-            None if logit is None else logit.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-            torch.cuda.current_stream().cuda_stream)
-    _native.check(st, "mlp_tail_forward")
+    launch("gps_mlp_tail_forward", n, d, int(h.dtype == torch.bfloat16), h, h.stride(0), gamma, beta, float(eps),
+           *_seed_args(p, seed, seed_dev), w2, b2, keep8, z16, logit, mean, rstd, device=dev,
+           label=f"mlp_tail_forward(rows={n},d={d})", nbytes=n * d * (h.element_size() + (2 if want_z16 else 0)) + 12 * n,
+           what="mlp_tail_forward")
     return z16, logit, mean, rstd
 
 
@@ -112,19 +107,12 @@ def tail_backward(h: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, mean
     dgamma, dbeta = torch.empty(d, **f), torch.empty(d, **f)
     dw2 = torch.empty(d, **f) if dlogit is not None else None
     db2 = torch.empty(1, **f) if dlogit is not None else None
-    lib = _native.load()
-    partial = torch.empty(int(lib.gps_mlp_tail_partial_rows(n)) * (3 * d + 4), **f)
-    from ...pointnet2._ext import _timed
+    partial = torch.empty(int(_native.load().gps_mlp_tail_partial_rows(n)) * (3 * d + 4), **f)
     nbytes = n * d * (2 * h.element_size() + (2 if dz16 is not None else 0)) + 12 * n + 4 * partial.numel()
-    with torch.cuda.device(dev), _timed(f"mlp_tail_backward(rows={n},d={d})", nbytes):
-        st = lib.gps_mlp_tail_backward(
-            n, d, int(h.dtype == torch.bfloat16), h.data_ptr(), h.stride(0), gamma.data_ptr(), beta.data_ptr(),
-            mean.data_ptr(), rstd.data_ptr(), *_seed_args(p, seed, seed_dev), None if w2 is None else w2.data_ptr(),
-            None if keep8 is None else keep8.data_ptr(), None if dlogit is None else dlogit.data_ptr(),
-            None if dz16 is None else dz16.data_ptr(), dpre.data_ptr(), dpre.stride(0), dgamma.data_ptr(), dbeta.data_ptr(),
-            None if dw2 is None else dw2.data_ptr(), None if db2 is None else db2.data_ptr(), partial.data_ptr(),
-            _native.ticket(dev, "mlp_tail").data_ptr(), torch.cuda.current_stream().cuda_stream)
-    _native.check(st, "mlp_tail_backward")
+    launch("gps_mlp_tail_backward", n, d, int(h.dtype == torch.bfloat16), h, h.stride(0), gamma, beta, mean, rstd,
+           *_seed_args(p, seed, seed_dev), w2, keep8, dlogit, dz16, dpre, dpre.stride(0), dgamma, dbeta, dw2, db2, partial,
+           _native.ticket(dev, "mlp_tail"), device=dev, label=f"mlp_tail_backward(rows={n},d={d})", nbytes=nbytes,
+           what="mlp_tail_backward")
     return dpre, dgamma, dbeta, dw2, db2
 
 

@@ -7,6 +7,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from ..._launch import launch
 from ..build import LANGUAGE_REGISTRY
 
 # GPU fast path of the encoder stack: the HuggingFace PARAMETERS and embedding
@@ -113,14 +114,8 @@ class _SelectRows(torch.autograd.Function):
 
     @staticmethod
     def _move(n, src, src_idx, dst, dst_idx, rows_live, zero_dead):
-        from ... import _native
-        with torch.cuda.device(src.device):
-            st = _native.load().gps_rows_move(n, src.shape[0], dst.shape[0], src.shape[1] * src.element_size(), src.data_ptr(),
-                                              None if src_idx is None else src_idx.data_ptr(), dst.data_ptr(),
-                                              None if dst_idx is None else dst_idx.data_ptr(),
-                                              None if rows_live is None else rows_live.data_ptr(),
-                                              int(zero_dead), torch.cuda.current_stream().cuda_stream)
-        _native.check(st, "rows_move")
+        launch("gps_rows_move", n, src.shape[0], dst.shape[0], src.shape[1] * src.element_size(), src, src_idx, dst, dst_idx,
+               rows_live, int(zero_dead), device=src.device)
 
     @staticmethod
     def forward(ctx, x, sel, rows_live):

@@ -17,6 +17,8 @@ import torch
 import torch.nn.functional as F
 
 from ... import _native
+from ..._launch import launch
+from ..layers.fused_norm import _reduce_scratch, _row_fraction
 
 
 class _WordLookup(torch.autograd.Function):
@@ -47,13 +49,9 @@ def embedding_grad(ids: torch.Tensor, dy: torch.Tensor, num_rows: int, padding_i
     n = ids1.numel()
     out = torch.empty((num_rows, d), dtype=torch.float32, device=dy2.device)
     scratch = torch.empty(int(_native.load().gps_embedding_grad_scratch_ints(n, num_rows, d)), dtype=torch.int32, device=dy2.device)
-    from ...pointnet2._ext import _timed
-    with torch.cuda.device(dy2.device), _timed(f"embedding_grad(n={n},rows={num_rows},d={d})",
-                                               4 * n * d + 8 * n + 4 * num_rows * d):
-        st = _native.load().gps_embedding_grad(n, d, num_rows, ids1.data_ptr(), dy2.data_ptr(), dy2.stride(0),
-                                               int(padding_idx), scratch.data_ptr(), out.data_ptr(),
-                                               torch.cuda.current_stream(dy2.device).cuda_stream)
-    _native.check(st, "embedding_grad")
+    launch("gps_embedding_grad", n, d, num_rows, ids1, dy2, dy2.stride(0), int(padding_idx), scratch, out, device=dy2.device,
+           label=f"embedding_grad(n={n},rows={num_rows},d={d})", nbytes=4 * n * d + 8 * n + 4 * num_rows * d,
+           what="embedding_grad")
     return out
 
 
@@ -110,16 +108,9 @@ class _BertEmbedRows(torch.autograd.Function):
         y16 = torch.empty((n, d), dtype=torch.bfloat16, device=dev)
         mean = torch.empty(n, dtype=torch.float32, device=dev)
         rstd = torch.empty(n, dtype=torch.float32, device=dev)
-        from ...pointnet2._ext import _timed
-        from ..layers.fused_norm import _ptr, _row_fraction
-        with torch.cuda.device(dev), _timed(f"bert_embed_forward(rows={n},d={d})", n * (d * (4 + 4 + 2) + 16),
-                                            work_fraction=_row_fraction(rows_dev, n)):
-            st = _native.load().gps_bert_embed_forward(
-                n, d, ids.data_ptr(), pos.data_ptr(), word_w.data_ptr(), pos_w.data_ptr(), type0.data_ptr(),
-                gamma.data_ptr(), beta.data_ptr(), float(eps), float(p_drop), 0, _ptr(seed_dev), y.data_ptr(),
-                y16.data_ptr(), mean.data_ptr(), rstd.data_ptr(), _ptr(rows_dev), _ptr(poison_dev),
-                torch.cuda.current_stream(dev).cuda_stream)
-        _native.check(st, "bert_embed_forward")
+        launch("gps_bert_embed_forward", n, d, ids, pos, word_w, pos_w, type0, gamma, beta, float(eps), float(p_drop), 0,
+               seed_dev, y, y16, mean, rstd, rows_dev, poison_dev, device=dev, label=f"bert_embed_forward(rows={n},d={d})",
+               nbytes=n * (d * (4 + 4 + 2) + 16), work_fraction=_row_fraction(rows_dev, n), what="bert_embed_forward")
         ctx.save_for_backward(ids, pos, word_w, pos_w, type0, gamma, mean, rstd, seed_dev, rows_dev, cu_rows)
         ctx.meta = (float(p_drop), int(padding_idx), type_w.shape[0])
         return y, y16
@@ -134,32 +125,20 @@ class _BertEmbedRows(torch.autograd.Function):
             dy = torch.zeros((n, d), dtype=torch.float32, device=dev)
         dy = dy.reshape(n, d).float().contiguous()
         dy16 = dy16.reshape(n, d).to(torch.bfloat16).contiguous() if dy16 is not None else None
-        lib = _native.load()
-        parts = int(lib.gps_bert_embed_partial_rows(n))
+        parts = int(_native.load().gps_bert_embed_partial_rows(n))
         part = torch.empty((2, parts, d), dtype=torch.float32, device=dev)
         dz = torch.empty((n, d), dtype=torch.float32, device=dev)
-        from ...pointnet2._ext import _timed
-        from ..layers.fused_norm import _ptr, _reduce_scratch, _row_fraction
-        with torch.cuda.device(dev), _timed(f"bert_embed_backward(rows={n},d={d})", n * (d * (4 + 2 + 4 + 4) + 24),
-                                            work_fraction=_row_fraction(rows_dev, n)):
-            st = lib.gps_bert_embed_backward(
-                n, d, dy.data_ptr(), _ptr(dy16), ids.data_ptr(), pos.data_ptr(), word_w.data_ptr(), pos_w.data_ptr(),
-                type0.data_ptr(), gamma.data_ptr(), mean.data_ptr(), rstd.data_ptr(), p_drop, 0, _ptr(seed_dev),
-                dz.data_ptr(), part[0].data_ptr(), part[1].data_ptr(), _ptr(rows_dev), torch.cuda.current_stream(dev).cuda_stream)
-        _native.check(st, "bert_embed_backward")
+        launch("gps_bert_embed_backward", n, d, dy, dy16, ids, pos, word_w, pos_w, type0, gamma, mean, rstd, p_drop, 0,
+               seed_dev, dz, part[0], part[1], rows_dev, device=dev, label=f"bert_embed_backward(rows={n},d={d})",
+               nbytes=n * (d * (4 + 2 + 4 + 4) + 24), work_fraction=_row_fraction(rows_dev, n), what="bert_embed_backward")
         sums = torch.empty((2, d), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            st = lib.gps_ln_reduce_partials(parts, d, part.data_ptr(), sums.data_ptr(), _reduce_scratch(dev, d).data_ptr(),
-                                            torch.cuda.current_stream(dev).cuda_stream)
-        _native.check(st, "ln_reduce_partials")
+        launch("gps_ln_reduce_partials", parts, d, part, sums, _reduce_scratch(dev, d), device=dev)
         d_word = embedding_grad(ids, dz, word_w.shape[0], padding_idx)
         if cu_rows is not None:      # whole sequences end to end, position = offset inside the sequence
             d_pos = torch.empty((pos_w.shape[0], d), dtype=torch.float32, device=dev)
-            with torch.cuda.device(dev), _timed(f"bert_position_grad(seqs={cu_rows.numel() - 1},d={d})", n * d * 4,
-                                                work_fraction=_row_fraction(rows_dev, n)):
-                st = lib.gps_bert_position_grad(cu_rows.numel() - 1, pos_w.shape[0], d, cu_rows.data_ptr(), dz.data_ptr(),
-                                                d_pos.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-            _native.check(st, "bert_position_grad")
+            launch("gps_bert_position_grad", cu_rows.numel() - 1, pos_w.shape[0], d, cu_rows, dz, d_pos, device=dev,
+                   label=f"bert_position_grad(seqs={cu_rows.numel() - 1},d={d})", nbytes=n * d * 4,
+                   work_fraction=_row_fraction(rows_dev, n), what="bert_position_grad")
         else:
             d_pos = embedding_grad(pos, dz, pos_w.shape[0], -1)
         d_type = torch.zeros((n_types, d), dtype=torch.float32, device=dev)
@@ -235,10 +214,7 @@ def varlen_plan(texts, n_seq_full: int = 0) -> VarlenPlan:
         arr[i].ids, arr[i].mask = ids_c.data_ptr(), m_c.data_ptr()
         arr[i].mask_elem_bytes, arr[i].mask_is_float = m_c.element_size(), int(m_c.is_floating_point())
         arr[i].n_seq, arr[i].len = ids.shape[0], ids.shape[1]
-    with torch.cuda.device(dev):
-        st = _native.load().gps_varlen_plan(arr, len(texts), int(n_seq_full), i32.data_ptr(), i64.data_ptr(),
-                                            valid.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-    _native.check(st, "varlen_plan")
+    launch("gps_varlen_plan", arr, len(texts), int(n_seq_full), i32, i64, valid, device=dev)
     p = VarlenPlan()
     p.lens, p.cu, p.order, p.q_limit = i32[:S], i32[S:2 * S + 1], i32[2 * S + 1:3 * S + 1], i32[3 * S + 1:4 * S + 1]
     p.n_valid, p.n_live_full, p.rows_tail = i32[4 * S + 1:4 * S + 2], i32[4 * S + 2:4 * S + 3], i32[4 * S + 3:4 * S + 4]

@@ -23,6 +23,7 @@ from typing import Optional
 import torch
 
 from ... import _native
+from ..._launch import launch, profiling, ptr
 
 HEAD_DIM = 64
 SPATIAL_VEC = 6
@@ -37,14 +38,6 @@ def supported(d_model: int, n_head: int, length: int, dtype: torch.dtype = torch
     cap = MAX_LEN_F32 if dtype == torch.float32 else MAX_LEN
     kv = length if kv_length is None else kv_length
     return d_model == n_head * HEAD_DIM and 0 < length <= cap and 0 < kv <= cap
-
-
-def _stream() -> int:
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return t.data_ptr() if t is not None else None
 
 
 # spatial self-attention rows served by the plane form of the pairwise term: gps_attention_sp.hip up to 144 rows,
@@ -90,19 +83,15 @@ def _mask8(mask: Optional[torch.Tensor]):
 
 
 def _call(backward: bool, name: str, nbytes: int, flops: int, work_fraction=None, **f) -> None:
-    """One gps_attn_forward_ex / gps_attn_backward_ex launch on the current stream (tensors -> pointers and pitches)."""
+    """One gps_attn_forward_ex / gps_attn_backward_ex launch on the current stream of the device of `out` (tensors ->
+    pointers and pitches)."""
     import ctypes
-
-    from ...pointnet2._ext import _timed
     a = _native.AttnArgs()
     for k, v in f.items():
         setattr(a, k, v.data_ptr() if torch.is_tensor(v) else v)
-    lib = _native.load()
-    fn = lib.gps_attn_backward_ex if backward else lib.gps_attn_forward_ex
     mfma = "fp32" if a.dtype == _native.ATTN_F32 else ("fp8" if (a.compute == _native.ATTN_COMPUTE_FP8 and not backward) else "bf16")
-    with _timed(name, nbytes, flops, mfma, work_fraction):
-        st = fn(ctypes.byref(a), _stream())
-    _native.check(st, name)
+    launch("gps_attn_backward_ex" if backward else "gps_attn_forward_ex", ctypes.byref(a), device=f["out"].device, label=name,
+           nbytes=nbytes, flops=flops, mfma=mfma, work_fraction=work_fraction)
 
 
 class _FusedSelfAttention(torch.autograd.Function):
@@ -129,11 +118,10 @@ class _FusedSelfAttention(torch.autograd.Function):
             from ..utils import pairwise_planes
             planes = pairwise_planes(pl)
             nbytes = esz * B * L * 4 * D + planes.numel() * 2 + B * L * n_head * 6 * 2
-            with torch.cuda.device(packed.device):
-                _call(False, f"attn_forward(L={L},spatial=1)", nbytes, 4 * B * n_head * L * L * HEAD_DIM,
-                      B=B, H=n_head, Lq=L, Lk=L, head_dim=HEAD_DIM, dtype=dt, compute=_native.ATTN_COMPUTE_NATIVE,
-                      q=base, ld_q=W, k=base + D * esz, v=base + 2 * D * esz, ld_kv=W, mask=_ptr(m8), p_drop=0.0, seed=0,
-                      out=out, ld_o=D, lse=lse, pl_planes=planes, ld_pl=planes.shape[-1], sw16=base + 3 * D * esz, ld_sw=W)
+            _call(False, f"attn_forward(L={L},spatial=1)", nbytes, 4 * B * n_head * L * L * HEAD_DIM,
+                  B=B, H=n_head, Lq=L, Lk=L, head_dim=HEAD_DIM, dtype=dt, compute=_native.ATTN_COMPUTE_NATIVE,
+                  q=base, ld_q=W, k=base + D * esz, v=base + 2 * D * esz, ld_kv=W, mask=ptr(m8), p_drop=0.0, seed=0,
+                  out=out, ld_o=D, lse=lse, pl_planes=planes, ld_pl=planes.shape[-1], sw16=base + 3 * D * esz, ld_sw=W)
             ctx.save_for_backward(packed, planes, m8, lse, out)
             ctx.meta = (n_head, 0.0, 0, "planes")
             return out
@@ -142,13 +130,12 @@ class _FusedSelfAttention(torch.autograd.Function):
             pl = pl.float().contiguous()
         # algorithmic work: q,k,v,out once (+ pairwise/cond vector), 2 x L x L x 64 MACs per head
         nbytes = esz * B * L * 4 * D + (B * L * L * 5 * 4 + B * L * n_head * 6 * 4 if spatial else 0)
-        with torch.cuda.device(packed.device):
-            _call(False, f"attn_forward(L={L},spatial={int(spatial)})" + ("[fp32]" if dt else "") + ("[fp8]" if fp8 else ""),
-                  nbytes, 4 * B * n_head * L * L * HEAD_DIM,
-                  B=B, H=n_head, Lq=L, Lk=L, head_dim=HEAD_DIM, dtype=dt,
-                  compute=_native.ATTN_COMPUTE_FP8 if fp8 else _native.ATTN_COMPUTE_NATIVE,
-                  q=base, ld_q=W, k=base + D * esz, v=base + 2 * D * esz, ld_kv=W, sw=_ptr(sw), pl=_ptr(pl), mask=_ptr(m8),
-                  p_drop=float(p_drop), seed=int(seed), seed_dev=_ptr(seed_dev), out=out, ld_o=D, lse=lse)
+        _call(False, f"attn_forward(L={L},spatial={int(spatial)})" + ("[fp32]" if dt else "") + ("[fp8]" if fp8 else ""),
+              nbytes, 4 * B * n_head * L * L * HEAD_DIM,
+              B=B, H=n_head, Lq=L, Lk=L, head_dim=HEAD_DIM, dtype=dt,
+              compute=_native.ATTN_COMPUTE_FP8 if fp8 else _native.ATTN_COMPUTE_NATIVE,
+              q=base, ld_q=W, k=base + D * esz, v=base + 2 * D * esz, ld_kv=W, sw=ptr(sw), pl=ptr(pl), mask=ptr(m8),
+              p_drop=float(p_drop), seed=int(seed), seed_dev=ptr(seed_dev), out=out, ld_o=D, lse=lse)
         ctx.save_for_backward(packed, sw, pl, m8, lse, seed_dev, out)
         ctx.meta = (n_head, float(p_drop), int(seed), spatial)
         return out
@@ -164,14 +151,13 @@ class _FusedSelfAttention(torch.autograd.Function):
             dpacked = torch.empty_like(packed)
             base, esz, gbase = packed.data_ptr(), packed.element_size(), dpacked.data_ptr()
             nbytes = esz * B * L * 9 * D + planes.numel() * 2 + 2 * B * L * n_head * 6 * 2
-            with torch.cuda.device(packed.device):
-                _call(True, f"attn_backward(L={L},spatial=1)", nbytes, 10 * B * n_head * L * L * HEAD_DIM,
-                      B=B, H=n_head, Lq=L, Lk=L, head_dim=HEAD_DIM, dtype=_native.ATTN_BF16, compute=_native.ATTN_COMPUTE_NATIVE,
-                      q=base, ld_q=W, k=base + D * esz, v=base + 2 * D * esz, ld_kv=W, mask=_ptr(m8), p_drop=0.0, seed=0,
-                      out=out, ld_o=D, lse=lse, dout=dout, dq=gbase, ld_dq=W, dk=gbase + D * esz, dv=gbase + 2 * D * esz,
-                      ld_dkv=W, pl_planes=planes, ld_pl=planes.shape[-1], sw16=base + 3 * D * esz, ld_sw=W,
-                      dsw16=gbase + 3 * D * esz, ld_dsw=W,
-                      delta_ws=_delta_ws(B, n_head, L, packed.device) if L > _RESIDENT_PLANES else None)
+            _call(True, f"attn_backward(L={L},spatial=1)", nbytes, 10 * B * n_head * L * L * HEAD_DIM,
+                  B=B, H=n_head, Lq=L, Lk=L, head_dim=HEAD_DIM, dtype=_native.ATTN_BF16, compute=_native.ATTN_COMPUTE_NATIVE,
+                  q=base, ld_q=W, k=base + D * esz, v=base + 2 * D * esz, ld_kv=W, mask=ptr(m8), p_drop=0.0, seed=0,
+                  out=out, ld_o=D, lse=lse, dout=dout, dq=gbase, ld_dq=W, dk=gbase + D * esz, dv=gbase + 2 * D * esz,
+                  ld_dkv=W, pl_planes=planes, ld_pl=planes.shape[-1], sw16=base + 3 * D * esz, ld_sw=W,
+                  dsw16=gbase + 3 * D * esz, ld_dsw=W,
+                  delta_ws=_delta_ws(B, n_head, L, packed.device) if L > _RESIDENT_PLANES else None)
             return dpacked, None, None, None, None, None, None
         packed, sw, pl, m8, lse, seed_dev, out = ctx.saved_tensors
         B, L, W = packed.shape
@@ -184,13 +170,12 @@ class _FusedSelfAttention(torch.autograd.Function):
         gbase = dpacked.data_ptr()
         nbytes = esz * B * L * 8 * D + (B * L * L * 5 * 4 + 2 * B * L * n_head * 6 * 4 if spatial else 0)
         delta = _delta_ws(B, n_head, L, packed.device) if (not spatial and dt == _native.ATTN_BF16) else None
-        with torch.cuda.device(packed.device):
-            _call(True, f"attn_backward(L={L},spatial={int(spatial)})" + ("[fp32]" if dt else ""),
-                  nbytes, 10 * B * n_head * L * L * HEAD_DIM,
-                  B=B, H=n_head, Lq=L, Lk=L, head_dim=HEAD_DIM, dtype=dt, compute=_native.ATTN_COMPUTE_NATIVE,
-                  q=base, ld_q=W, k=base + D * esz, v=base + 2 * D * esz, ld_kv=W, sw=_ptr(sw), pl=_ptr(pl), mask=_ptr(m8),
-                  p_drop=p_drop, seed=seed, seed_dev=_ptr(seed_dev), out=out, ld_o=D, lse=lse, dout=dout,
-                  dq=gbase, ld_dq=W, dk=gbase + D * esz, dv=gbase + 2 * D * esz, ld_dkv=W, dsw=_ptr(dsw), delta_ws=_ptr(delta))
+        _call(True, f"attn_backward(L={L},spatial={int(spatial)})" + ("[fp32]" if dt else ""),
+              nbytes, 10 * B * n_head * L * L * HEAD_DIM,
+              B=B, H=n_head, Lq=L, Lk=L, head_dim=HEAD_DIM, dtype=dt, compute=_native.ATTN_COMPUTE_NATIVE,
+              q=base, ld_q=W, k=base + D * esz, v=base + 2 * D * esz, ld_kv=W, sw=ptr(sw), pl=ptr(pl), mask=ptr(m8),
+              p_drop=p_drop, seed=seed, seed_dev=ptr(seed_dev), out=out, ld_o=D, lse=lse, dout=dout,
+              dq=gbase, ld_dq=W, dk=gbase + D * esz, dv=gbase + 2 * D * esz, ld_dkv=W, dsw=ptr(dsw), delta_ws=ptr(delta))
         if spatial:
             dpacked[..., 3 * D:] = dsw
         return dpacked, None, None, None, None, None, None
@@ -215,13 +200,12 @@ class _FusedCrossAttention(torch.autograd.Function):
         esz = q.element_size()
         fp8 = _FP8 and dt == _native.ATTN_BF16
         nbytes = esz * B * (2 * Lq + 2 * Lk) * D
-        with torch.cuda.device(q.device):
-            _call(False, f"xattn_forward(Lq={Lq},Lk={Lk})" + ("[fp32]" if dt else "") + ("[fp8]" if fp8 else ""),
-                  nbytes, 4 * B * n_head * Lq * Lk * HEAD_DIM,
-                  B=B, H=n_head, Lq=Lq, Lk=Lk, head_dim=HEAD_DIM, dtype=dt,
-                  compute=_native.ATTN_COMPUTE_FP8 if fp8 else _native.ATTN_COMPUTE_NATIVE,
-                  q=q, ld_q=D, k=kv.data_ptr(), v=kv.data_ptr() + D * esz, ld_kv=2 * D, mask=_ptr(m8),
-                  p_drop=float(p_drop), seed=0, seed_dev=_ptr(seed_dev), out=out, ld_o=D, lse=lse)
+        _call(False, f"xattn_forward(Lq={Lq},Lk={Lk})" + ("[fp32]" if dt else "") + ("[fp8]" if fp8 else ""),
+              nbytes, 4 * B * n_head * Lq * Lk * HEAD_DIM,
+              B=B, H=n_head, Lq=Lq, Lk=Lk, head_dim=HEAD_DIM, dtype=dt,
+              compute=_native.ATTN_COMPUTE_FP8 if fp8 else _native.ATTN_COMPUTE_NATIVE,
+              q=q, ld_q=D, k=kv.data_ptr(), v=kv.data_ptr() + D * esz, ld_kv=2 * D, mask=ptr(m8),
+              p_drop=float(p_drop), seed=0, seed_dev=ptr(seed_dev), out=out, ld_o=D, lse=lse)
         ctx.save_for_backward(q, kv, m8, lse, seed_dev, out)
         ctx.meta = (n_head, float(p_drop))
         return out
@@ -237,14 +221,13 @@ class _FusedCrossAttention(torch.autograd.Function):
         dq, dkv = torch.empty_like(q), torch.empty_like(kv)
         esz = q.element_size()
         nbytes = esz * B * (4 * Lq + 4 * Lk) * D
-        with torch.cuda.device(q.device):
-            _call(True, f"xattn_backward(Lq={Lq},Lk={Lk})" + ("[fp32]" if dt else ""),
-                  nbytes, 10 * B * n_head * Lq * Lk * HEAD_DIM,
-                  B=B, H=n_head, Lq=Lq, Lk=Lk, head_dim=HEAD_DIM, dtype=dt, compute=_native.ATTN_COMPUTE_NATIVE,
-                  q=q, ld_q=D, k=kv.data_ptr(), v=kv.data_ptr() + D * esz, ld_kv=2 * D, mask=_ptr(m8),
-                  p_drop=p_drop, seed=0, seed_dev=_ptr(seed_dev), out=out, ld_o=D, lse=lse, dout=dout,
-                  dq=dq, ld_dq=D, dk=dkv.data_ptr(), dv=dkv.data_ptr() + D * esz, ld_dkv=2 * D,
-                  delta_ws=_ptr(_delta_ws(B, n_head, Lq, q.device) if dt == _native.ATTN_BF16 else None))
+        _call(True, f"xattn_backward(Lq={Lq},Lk={Lk})" + ("[fp32]" if dt else ""),
+              nbytes, 10 * B * n_head * Lq * Lk * HEAD_DIM,
+              B=B, H=n_head, Lq=Lq, Lk=Lk, head_dim=HEAD_DIM, dtype=dt, compute=_native.ATTN_COMPUTE_NATIVE,
+              q=q, ld_q=D, k=kv.data_ptr(), v=kv.data_ptr() + D * esz, ld_kv=2 * D, mask=ptr(m8),
+              p_drop=p_drop, seed=0, seed_dev=ptr(seed_dev), out=out, ld_o=D, lse=lse, dout=dout,
+              dq=dq, ld_dq=D, dk=dkv.data_ptr(), dv=dkv.data_ptr() + D * esz, ld_dkv=2 * D,
+              delta_ws=ptr(_delta_ws(B, n_head, Lq, q.device) if dt == _native.ATTN_BF16 else None))
         return dq, dkv, None, None, None, None
 
 
@@ -266,13 +249,12 @@ class _FusedVarlenSelfAttention(torch.autograd.Function):
         lse = torch.empty((n_seq, n_head, cap), dtype=torch.float32, device=packed.device)
         base, esz = packed.data_ptr(), packed.element_size()
         frac = _varlen_fraction(cu_rows, n_seq, cap)
-        with torch.cuda.device(packed.device):
-            _call(False, f"attn_forward(L<={cap},varlen,seqs={n_seq})", esz * n_seq * cap * 4 * D,
-                  4 * n_seq * n_head * cap * cap * HEAD_DIM, work_fraction=frac,
-                  B=n_seq, H=n_head, Lq=cap, Lk=cap, head_dim=HEAD_DIM, dtype=_native.ATTN_BF16,
-                  compute=_native.ATTN_COMPUTE_NATIVE, q=base, ld_q=W, k=base + D * esz, v=base + 2 * D * esz, ld_kv=W,
-                  p_drop=float(p_drop), seed=0, seed_dev=_ptr(seed_dev), out=out, ld_o=D, lse=lse, cu_rows=cu_rows,
-                  seq_order=_ptr(order), q_limit=_ptr(q_limit))
+        _call(False, f"attn_forward(L<={cap},varlen,seqs={n_seq})", esz * n_seq * cap * 4 * D,
+              4 * n_seq * n_head * cap * cap * HEAD_DIM, work_fraction=frac,
+              B=n_seq, H=n_head, Lq=cap, Lk=cap, head_dim=HEAD_DIM, dtype=_native.ATTN_BF16,
+              compute=_native.ATTN_COMPUTE_NATIVE, q=base, ld_q=W, k=base + D * esz, v=base + 2 * D * esz, ld_kv=W,
+              p_drop=float(p_drop), seed=0, seed_dev=ptr(seed_dev), out=out, ld_o=D, lse=lse, cu_rows=cu_rows,
+              seq_order=ptr(order), q_limit=ptr(q_limit))
         ctx.save_for_backward(packed, cu_rows, lse, seed_dev, out, order, q_limit)
         ctx.meta = (n_seq, cap, n_head, float(p_drop))
         return out
@@ -287,14 +269,13 @@ class _FusedVarlenSelfAttention(torch.autograd.Function):
         dpacked = torch.empty_like(packed)
         base, esz, gbase = packed.data_ptr(), packed.element_size(), dpacked.data_ptr()
         frac = _varlen_fraction(cu_rows, n_seq, cap)
-        with torch.cuda.device(packed.device):
-            _call(True, f"attn_backward(L<={cap},varlen,seqs={n_seq})", esz * n_seq * cap * 8 * D,
-                  10 * n_seq * n_head * cap * cap * HEAD_DIM, work_fraction=frac,
-                  B=n_seq, H=n_head, Lq=cap, Lk=cap, head_dim=HEAD_DIM, dtype=_native.ATTN_BF16,
-                  compute=_native.ATTN_COMPUTE_NATIVE, q=base, ld_q=W, k=base + D * esz, v=base + 2 * D * esz, ld_kv=W,
-                  p_drop=p_drop, seed=0, seed_dev=_ptr(seed_dev), out=out, ld_o=D, lse=lse, dout=dout,
-                  dq=gbase, ld_dq=W, dk=gbase + D * esz, dv=gbase + 2 * D * esz, ld_dkv=W, cu_rows=cu_rows,
-                  seq_order=_ptr(order), q_limit=_ptr(q_limit), delta_ws=_delta_ws(n_seq, n_head, cap, packed.device))
+        _call(True, f"attn_backward(L<={cap},varlen,seqs={n_seq})", esz * n_seq * cap * 8 * D,
+              10 * n_seq * n_head * cap * cap * HEAD_DIM, work_fraction=frac,
+              B=n_seq, H=n_head, Lq=cap, Lk=cap, head_dim=HEAD_DIM, dtype=_native.ATTN_BF16,
+              compute=_native.ATTN_COMPUTE_NATIVE, q=base, ld_q=W, k=base + D * esz, v=base + 2 * D * esz, ld_kv=W,
+              p_drop=p_drop, seed=0, seed_dev=ptr(seed_dev), out=out, ld_o=D, lse=lse, dout=dout,
+              dq=gbase, ld_dq=W, dk=gbase + D * esz, dv=gbase + 2 * D * esz, ld_dkv=W, cu_rows=cu_rows,
+              seq_order=ptr(order), q_limit=ptr(q_limit), delta_ws=_delta_ws(n_seq, n_head, cap, packed.device))
         return dpacked, None, None, None, None, None, None, None, None
 
 
@@ -322,7 +303,6 @@ def set_plain_blocks(flag: bool) -> int:
 
 def _varlen_fraction(cu_rows: torch.Tensor, n_seq: int, cap: int):
     """bench accounting: sum L_b^2 / (B cap^2), read back at profile_stop() from a snapshot of the offsets."""
-    from ...pointnet2._ext import profiling
     if not profiling():
         return None
     snap = cu_rows.detach().clone()

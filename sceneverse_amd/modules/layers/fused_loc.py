@@ -9,6 +9,7 @@ import torch
 from torch import nn
 
 from ... import _native
+from ..._launch import launch
 
 _ENABLED = True
 
@@ -29,13 +30,8 @@ class _LocEmbed(torch.autograd.Function):
         y = torch.empty((n, d), dtype=torch.float32, device=x.device)
         mean = torch.empty(n, dtype=torch.float32, device=x.device)
         rstd = torch.empty(n, dtype=torch.float32, device=x.device)
-        from ...pointnet2._ext import _timed
-        with torch.cuda.device(x.device), _timed(f"loc_embed_forward(rows={n},k={k_in},d={d})", n * (d + k_in) * 4):
-            st = _native.load().gps_loc_embed_forward(
-                n, k_in, d, x2.data_ptr(), w32.data_ptr(), b32.data_ptr() if b32 is not None else None, g32.data_ptr(),
-                bt32.data_ptr(), float(eps), y.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                torch.cuda.current_stream(x.device).cuda_stream)
-        _native.check(st, "loc_embed_forward")
+        launch("gps_loc_embed_forward", n, k_in, d, x2, w32, b32, g32, bt32, float(eps), y, mean, rstd, device=x.device,
+               label=f"loc_embed_forward(rows={n},k={k_in},d={d})", nbytes=n * (d + k_in) * 4, what="loc_embed_forward")
         ctx.save_for_backward(x2, w32, b32, g32, mean, rstd)
         ctx.out_shape = x.shape[:-1] + (d,)
         return y.view(ctx.out_shape)
@@ -46,17 +42,11 @@ class _LocEmbed(torch.autograd.Function):
         n, k_in = x2.shape
         d = w32.shape[0]
         dy2 = dy.reshape(n, d).float().contiguous()
-        lib = _native.load()
-        parts = int(lib.gps_loc_embed_partial_rows(n))
+        parts = int(_native.load().gps_loc_embed_partial_rows(n))
         scratch = torch.empty((parts, k_in + 3, d), dtype=torch.float32, device=x2.device)
         sums = torch.empty((k_in + 3, d), dtype=torch.float32, device=x2.device)
-        from ...pointnet2._ext import _timed
-        with torch.cuda.device(x2.device), _timed(f"loc_embed_backward(rows={n},k={k_in},d={d})", n * (d + k_in) * 4):
-            st = lib.gps_loc_embed_backward(
-                n, k_in, d, dy2.data_ptr(), x2.data_ptr(), w32.data_ptr(), b32.data_ptr() if b32 is not None else None,
-                g32.data_ptr(), mean.data_ptr(), rstd.data_ptr(), scratch.data_ptr(), sums.data_ptr(),
-                torch.cuda.current_stream(x2.device).cuda_stream)
-        _native.check(st, "loc_embed_backward")
+        launch("gps_loc_embed_backward", n, k_in, d, dy2, x2, w32, b32, g32, mean, rstd, scratch, sums, device=x2.device,
+               label=f"loc_embed_backward(rows={n},k={k_in},d={d})", nbytes=n * (d + k_in) * 4, what="loc_embed_backward")
         dw = sums[:k_in].t().contiguous()                        # (d, k_in)
         return None, dw, (sums[k_in] if b32 is not None else None), sums[k_in + 1], sums[k_in + 2], None
 

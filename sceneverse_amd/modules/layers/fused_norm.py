@@ -11,6 +11,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from ... import _native
+from ..._launch import launch, profiling
 
 _ENABLED = True
 
@@ -34,13 +35,8 @@ def _reduce_scratch(device: torch.device, d: int) -> torch.Tensor:
     return buf
 
 
-def _ptr(t: Optional[torch.Tensor]):
-    return t.data_ptr() if t is not None else None
-
-
 def _row_fraction(rows_dev: Optional[torch.Tensor], n: int):
     """bench accounting: share of the static row count a launch with a device-side row count really touches."""
-    from ...pointnet2._ext import profiling
     if rows_dev is None or not profiling() or n == 0:
         return None
     snap = rows_dev.detach().clone()
@@ -78,16 +74,10 @@ class _AddDropoutLN(torch.autograd.Function):
         y16 = torch.empty((n, d), dtype=torch.bfloat16, device=x.device) if want_bf16 else None
         mean = torch.empty(n, dtype=torch.float32, device=x.device)
         rstd = torch.empty(n, dtype=torch.float32, device=x.device)
-        from ...pointnet2._ext import _timed
-        nbytes = n * d * (2 * x2.element_size() + h2.element_size())
-        with torch.cuda.device(x.device), _timed(f"add_dropout_layernorm_forward(rows={n},d={d})", nbytes,
-                                                 work_fraction=_row_fraction(rows_dev, n)):
-            st = _native.load().gps_add_dropout_layernorm_forward_post(
-                n, d, int(x2.dtype == torch.bfloat16), int(h2.dtype == torch.bfloat16), x2.data_ptr(),
-                h2.data_ptr(), g32.data_ptr(), b32.data_ptr(), float(eps), float(p_drop), 0, _ptr(seed_dev),
-                y.data_ptr(), _ptr(y16), mean.data_ptr(), rstd.data_ptr(), _ptr(rows_dev), _ptr(post2),
-                torch.cuda.current_stream().cuda_stream)
-        _native.check(st, "add_dropout_layernorm_forward")
+        launch("gps_add_dropout_layernorm_forward_post", n, d, int(x2.dtype == torch.bfloat16), int(h2.dtype == torch.bfloat16),
+               x2, h2, g32, b32, float(eps), float(p_drop), 0, seed_dev, y, y16, mean, rstd, rows_dev, post2, device=x.device,
+               label=f"add_dropout_layernorm_forward(rows={n},d={d})", nbytes=n * d * (2 * x2.element_size() + h2.element_size()),
+               work_fraction=_row_fraction(rows_dev, n), what="add_dropout_layernorm_forward")
         ctx.save_for_backward(x2, h2, g32, mean, rstd, seed_dev, rows_dev)
         ctx.meta = (float(p_drop), x.shape, h.shape, gamma.dtype, beta.dtype)
         ctx.ln_params = (gamma, beta)                       # the parameter OBJECTS (deferred dgamma / dbeta, see backward)
@@ -118,19 +108,13 @@ class _AddDropoutLN(torch.autograd.Function):
                 dpost.zero_()                                  # rows past the device count are not written
             if share is not None:
                 share.buf = dpost
-        lib = _native.load()
-        parts = int(lib.gps_ln_partial_rows(n))
+        parts = int(_native.load().gps_ln_partial_rows(n))
         part = torch.empty((2, parts, d), dtype=torch.float32, device=x2.device)
-        from ...pointnet2._ext import _timed
-        nbytes = n * d * (3 * x2.element_size() + 2 * h2.element_size())
-        with torch.cuda.device(x2.device), _timed(f"add_dropout_layernorm_backward(rows={n},d={d})", nbytes,
-                                                  work_fraction=_row_fraction(rows_dev, n)):
-            st = lib.gps_add_dropout_layernorm_backward_post_acc(
-                n, d, int(x2.dtype == torch.bfloat16), int(h2.dtype == torch.bfloat16), dy2.data_ptr(),
-                _ptr(dy16_2), x2.data_ptr(), h2.data_ptr(), g32.data_ptr(), mean.data_ptr(), rstd.data_ptr(), p_drop, 0,
-                _ptr(seed_dev), dx.data_ptr(), dh.data_ptr(), part[0].data_ptr(), part[1].data_ptr(), _ptr(rows_dev),
-                _ptr(dpost), acc, torch.cuda.current_stream().cuda_stream)
-        _native.check(st, "add_dropout_layernorm_backward")
+        launch("gps_add_dropout_layernorm_backward_post_acc", n, d, int(x2.dtype == torch.bfloat16),
+               int(h2.dtype == torch.bfloat16), dy2, dy16_2, x2, h2, g32, mean, rstd, p_drop, 0, seed_dev, dx, dh, part[0], part[1],
+               rows_dev, dpost, acc, device=x2.device, label=f"add_dropout_layernorm_backward(rows={n},d={d})",
+               nbytes=n * d * (3 * x2.element_size() + 2 * h2.element_size()), work_fraction=_row_fraction(rows_dev, n),
+               what="add_dropout_layernorm_backward")
         if share is not None:
             if final:
                 share.buf = None                               # handed to autograd below; the next pass starts afresh
@@ -145,11 +129,7 @@ class _AddDropoutLN(torch.autograd.Function):
         if gemm.defer_ln_param_grads(part, parts, d, *ctx.ln_params, needs=(ctx.needs_input_grad[2], ctx.needs_input_grad[3])):
             return (dx.view(x_shape), dh.view(h_shape), None, None, None, None, None, None, None, dpost, None)
         sums = torch.empty((2, d), dtype=torch.float32, device=x2.device)
-        with torch.cuda.device(x2.device):
-            st = lib.gps_ln_reduce_partials(parts, d, part.data_ptr(), sums.data_ptr(),
-                                            _reduce_scratch(x2.device, d).data_ptr(),
-                                            torch.cuda.current_stream().cuda_stream)
-        _native.check(st, "ln_reduce_partials")
+        launch("gps_ln_reduce_partials", parts, d, part, sums, _reduce_scratch(x2.device, d), device=x2.device)
         return (dx.view(x_shape), dh.view(h_shape), sums[0].to(g_dtype), sums[1].to(b_dtype),
                 None, None, None, None, None, dpost, None)
 
@@ -200,10 +180,7 @@ class _L2Normalize(torch.autograd.Function):
         n = x2.shape[0]
         y = torch.empty_like(x2)
         inv = torch.empty(n, dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            st = _native.load().gps_l2_normalize_forward(n, d, x2.data_ptr(), float(eps), y.data_ptr(), inv.data_ptr(),
-                                                         torch.cuda.current_stream().cuda_stream)
-        _native.check(st, "l2_normalize_forward")
+        launch("gps_l2_normalize_forward", n, d, x2, float(eps), y, inv, device=x.device)
         ctx.save_for_backward(y, inv)
         ctx.eps = float(eps)
         return y.view(x.shape)
@@ -214,10 +191,7 @@ class _L2Normalize(torch.autograd.Function):
         n, d = y.shape
         dy2 = dy.reshape(n, d).float().contiguous()
         dx = torch.empty_like(y)
-        with torch.cuda.device(y.device):
-            st = _native.load().gps_l2_normalize_backward(n, d, dy2.data_ptr(), y.data_ptr(), inv.data_ptr(), ctx.eps,
-                                                          dx.data_ptr(), torch.cuda.current_stream().cuda_stream)
-        _native.check(st, "l2_normalize_backward")
+        launch("gps_l2_normalize_backward", n, d, dy2, y, inv, ctx.eps, dx, device=y.device)
         return dx.view(dy.shape), None
 
 
@@ -276,10 +250,7 @@ def column_sum(x: torch.Tensor) -> torch.Tensor:
     x2 = x2.contiguous()
     half = n // 2                                               # the reducer sums two stacked sets of `half` rows
     sums = torch.empty((2, d), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        st = _native.load().gps_ln_reduce_partials(half, d, x2.data_ptr(), sums.data_ptr(), _reduce_scratch(x.device, d).data_ptr(),
-                                                   torch.cuda.current_stream().cuda_stream)
-    _native.check(st, "ln_reduce_partials")
+    launch("gps_ln_reduce_partials", half, d, x2, sums, _reduce_scratch(x.device, d), device=x.device)
     out = sums[0] + sums[1]
     return out + x2[2 * half] if n & 1 else out
 

@@ -31,6 +31,7 @@ from typing import Optional, Sequence
 import torch
 
 from ... import _native
+from ..._launch import launch, profiling, ptr
 from ..._native import (EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_GELU_FACTOR, EPI_BIAS_RELU, EPI_DGELU, EPI_DRELU, EPI_F32, EPI_MUL_AUX,
                         EPI_RELU_MAX16, EPI_RELU_SPLIT,
                         GEMM_NN, GEMM_NT,
@@ -64,14 +65,6 @@ def usable(x: torch.Tensor, in_features: int, out_features: int) -> bool:
         torch.get_autocast_dtype("cuda") == torch.bfloat16
 
 
-def _ptr(t: Optional[torch.Tensor]):
-    return t.data_ptr() if t is not None else None
-
-
-def _stream() -> int:
-    return torch.cuda.current_stream().cuda_stream
-
-
 _FORM_NAME = {GEMM_NT: "nt", GEMM_NN: "nn", GEMM_TN: "tn"}
 
 
@@ -93,12 +86,11 @@ def _product(form: int, epilogue: int, M: int, N: int, K: int, A: torch.Tensor, 
     a.variant = _VARIANT[form] if variant is None else variant
     a.reserved = 0
     a.A, a.lda, a.B, a.ldb, a.C, a.ldc = A.data_ptr(), lda, B.data_ptr(), ldb, C.data_ptr(), ldc
-    a.bias = _ptr(bias)
-    a.aux, a.ldaux, a.aux_out, a.ldaux_out = _ptr(aux), ldaux, _ptr(aux_out), ldaux_out
-    a.workspace, a.colsum, a.seed_dev = _ptr(workspace), _ptr(colsum), _ptr(seed_dev)
-    a.extent_dev = _ptr(extent_dev)
+    a.bias = ptr(bias)
+    a.aux, a.ldaux, a.aux_out, a.ldaux_out = ptr(aux), ldaux, ptr(aux_out), ldaux_out
+    a.workspace, a.colsum, a.seed_dev = ptr(workspace), ptr(colsum), ptr(seed_dev)
+    a.extent_dev = ptr(extent_dev)
     a.seed, a.p_drop = 0, float(p_drop)
-    from ...pointnet2._ext import profiling
     nbytes = 2 * (M * K + N * K) + {EPI_F32: 4 * M * N, EPI_RELU_SPLIT: 6 * M * N, EPI_RELU_MAX16: M * N // 4}.get(epilogue, 2 * M * N)
     work_fraction = None
     if extent_dev is not None and profiling():
@@ -121,10 +113,8 @@ def _product(form: int, epilogue: int, M: int, N: int, K: int, A: torch.Tensor, 
 
 
 def _launch(q: _Product) -> None:
-    from ...pointnet2._ext import _timed
-    with torch.cuda.device(q.device), _timed(q.name, q.nbytes, q.flops, "bf16", q.work_fraction):
-        st = _native.load().gps_gemm_bf16(ctypes.byref(q.args), _stream())
-    _native.check(st, q.name)
+    launch("gps_gemm_bf16", ctypes.byref(q.args), device=q.device, label=q.name, nbytes=q.nbytes, flops=q.flops, mfma="bf16",
+           work_fraction=q.work_fraction)
 
 
 _GROUPED = True          # False: the products of a twin call leave one by one (A/B, tests)
@@ -144,7 +134,6 @@ def _launch_together(products: Sequence[_Product]) -> None:
         for q in products:
             _launch(q)
         return
-    lib = _native.load()
     pending = list(products)
     while pending:
         head = pending[0]
@@ -155,7 +144,6 @@ def _launch_together(products: Sequence[_Product]) -> None:
             _launch(head)
             continue
         arr = (GemmArgs * len(same))(*[q.args for q in same])
-        from ...pointnet2._ext import _timed, profiling
         args = [q.args for q in same]
         name = (f"gemm_{_FORM_NAME[head.form]}_grouped(M={'+'.join(str(a.M) for a in args)},N={'+'.join(str(a.N) for a in args)},"
                 f"K={'+'.join(str(a.K) for a in args)},epi={head.epilogue})")
@@ -168,13 +156,11 @@ def _launch_together(products: Sequence[_Product]) -> None:
             nbytes = lambda _f: sum((q.nbytes(f) if callable(q.nbytes) else q.nbytes) for q, f in zip(same, live()))  # noqa: E731
         else:
             nbytes = 0
-        with torch.cuda.device(head.device), _timed(name, nbytes, flops, "bf16", work_fraction):
-            st = lib.gps_gemm_bf16_grouped(arr, len(same), _stream())
+        st = launch("gps_gemm_bf16_grouped", arr, len(same), device=head.device, label=name, nbytes=nbytes, flops=flops,
+                    mfma="bf16", work_fraction=work_fraction, accept=(_native.GPS_ERR_UNSUPPORTED,))
         if st == _native.GPS_ERR_UNSUPPORTED:
             for q in same:
                 _launch(q)
-        else:
-            _native.check(st, name)
 
 
 def gemm(form: int, epilogue: int, M: int, N: int, K: int, A: torch.Tensor, lda: int, B: torch.Tensor, ldb: int,
@@ -244,7 +230,7 @@ _WS = {}
 
 def _workspace(device, floats: int) -> torch.Tensor:
     """Split-K scratch, one growing buffer per device and stream (safe: launches on a stream are ordered)."""
-    key = (device, torch.cuda.current_stream(device).cuda_stream)
+    key = (device, torch.cuda.current_stream(device))
     buf = _WS.get(key)
     if buf is None or buf.numel() < floats:
         buf = _WS[key] = torch.empty(max(floats, 1 << 22), dtype=torch.float32, device=device)
@@ -444,9 +430,8 @@ def _flush_ln_param_grads() -> None:
             _GROUP["written"].update((id(gamma), id(beta)))
         if probs:
             arr = (LnReduceProblem * len(probs))(*probs)
-            with torch.cuda.device(dev):
-                st = lib.gps_ln_reduce_partials_grouped(arr, len(probs), d, scratch.data_ptr(), _stream())
-            _native.check(st, f"ln_reduce_partials_grouped({len(probs)} problems)")
+            launch("gps_ln_reduce_partials_grouped", arr, len(probs), d, scratch, device=dev,
+                   what=f"ln_reduce_partials_grouped({len(probs)} problems)")
     del items
 
 
@@ -480,7 +465,7 @@ def flush_grouped_wgrads() -> None:
                 q.B, q.ldb = x16.data_ptr(), x16.stride(0)
                 q.C, q.ldc = gw.data_ptr(), K_in
                 q.colsum = gb.data_ptr() if gb is not None else None
-                q.extent_dev = _ptr(rows_dev)
+                q.extent_dev = ptr(rows_dev)
                 probs.append(q)
                 prob_rows.append((dy16, x16, rows_dev))
                 _GROUP["written"].add(id(w))
@@ -491,7 +476,6 @@ def flush_grouped_wgrads() -> None:
     dev = items[0][0].device
     if probs:
         arr = (WgradProblem * len(probs))(*probs)
-        from ...pointnet2._ext import _timed, profiling
         flops = sum(2 * q.M * q.N * q.K for q in probs)
         nbytes = sum(2 * q.K * (q.M + q.N) + 4 * q.M * q.N for q in probs)
         work_fraction = None
@@ -509,9 +493,9 @@ def flush_grouped_wgrads() -> None:
 
             work_fraction = lambda: sum(2 * m * n * kk for (m, n, _), kk in zip(shapes, live())) / max(1, flops)  # noqa: E731
             nbytes = lambda f: sum(2 * kk * (m + n) + 4 * m * n for (m, n, _), kk in zip(shapes, live()))       # noqa: E731
-        with torch.cuda.device(dev), _timed(f"gemm_tn_grouped(problems={len(probs)})", nbytes, flops, "bf16", work_fraction):
-            st = _native.load().gps_gemm_wgrad_grouped(arr, len(probs), _stream())
-        _native.check(st, f"gemm_wgrad_grouped({len(probs)} problems)")
+        launch("gps_gemm_wgrad_grouped", arr, len(probs), device=dev, label=f"gemm_tn_grouped(problems={len(probs)})",
+               nbytes=nbytes, flops=flops, mfma="bf16", work_fraction=work_fraction,
+               what=f"gemm_wgrad_grouped({len(probs)} problems)")
     for dy16, x16, w, b, r, n, rows_dev in fallback:
         dw, db = linear_wgrad(dy16[:, r:r + n], x16, want_bias=b is not None, rows_dev=rows_dev)
         for t, g in ((w, dw), (b, db)):
@@ -606,9 +590,7 @@ def split3_points(xyz: torch.Tensor, feats: torch.Tensor, k_pad: int) -> torch.T
     C = feats.shape[1]
     xyz, feats = xyz.float().contiguous(), feats.float().contiguous()
     out = torch.empty((B * n, 3 * k_pad), dtype=torch.bfloat16, device=xyz.device)
-    with torch.cuda.device(xyz.device):
-        st = _native.load().gps_split3_points(B, n, C, xyz.data_ptr(), feats.data_ptr(), k_pad, out.data_ptr(), _stream())
-    _native.check(st, "split3_points")
+    launch("gps_split3_points", B, n, C, xyz, feats, k_pad, out, device=xyz.device)
     return out
 
 

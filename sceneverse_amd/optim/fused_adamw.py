@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from .. import _native
+from .._launch import launch
 
 
 class _TensorRec(ctypes.Structure):
@@ -184,13 +185,8 @@ class GpsAdamW(torch.optim.Optimizer):
             self._tables = self._build_tables(entries, gemm.shadow_targets())
             self._sig = sig
         tens, groups, chunks, partial, n_chunks, n_tensors = self._tables
-        with torch.cuda.device(self._device):
-            from ..pointnet2._ext import _timed
-            n = sum(p.numel() for p, _ in entries)
-            with _timed(f"adamw_step(params={n})", 28 * n + (4 * n if max_grad_norm else 0)):
-                st = _native.load().gps_adamw_step(n_tensors, n_chunks, tens.data_ptr(), groups.data_ptr(), chunks.data_ptr(),
-                                                   float(max_grad_norm) if max_grad_norm else 0.0, partial.data_ptr(),
-                                                   self._scalars.data_ptr(), self._steps.data_ptr(),
-                                                   torch.cuda.current_stream(self._device).cuda_stream)
-        _native.check(st, "adamw_step")
+        n = sum(p.numel() for p, _ in entries)
+        launch("gps_adamw_step", n_tensors, n_chunks, tens, groups, chunks, float(max_grad_norm) if max_grad_norm else 0.0, partial,
+               self._scalars, self._steps, device=self._device, label=f"adamw_step(params={n})",
+               nbytes=28 * n + (4 * n if max_grad_norm else 0), what="adamw_step")
         return loss

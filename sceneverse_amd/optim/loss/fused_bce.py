@@ -12,6 +12,7 @@ from typing import Optional
 import torch
 
 from ... import _native
+from ..._launch import launch
 from .fused_contra import _LDS_LIMIT, _rows_ok
 
 
@@ -32,17 +33,12 @@ class _BCELogitsSum(torch.autograd.Function):
         y = y.contiguous()
         w8 = None if weight is None else weight.to(torch.uint8).contiguous()
         dev = x.device
-        lib = _native.load()
-        partial = torch.empty(int(lib.gps_bce_logits_partial_floats(rows, cols)), dtype=torch.float32, device=dev)
+        partial = torch.empty(int(_native.load().gps_bce_logits_partial_floats(rows, cols)), dtype=torch.float32, device=dev)
         loss = torch.empty(1, dtype=torch.float32, device=dev)
-        from ...pointnet2._ext import _timed
         nbytes = x.numel() * x.element_size() + y.numel() * y.element_size() + (0 if w8 is None else w8.numel())
-        with torch.cuda.device(dev), _timed(f"bce_logits_forward(rows={rows},cols={cols})", nbytes):
-            st = lib.gps_bce_logits_forward(
-                rows, cols, int(x.dtype == torch.bfloat16), x.data_ptr(), x.stride(0), int(y.dtype == torch.float32),
-                y.data_ptr(), None if w8 is None else w8.data_ptr(), float(scale), partial.data_ptr(), loss.data_ptr(),
-                _native.ticket(dev, "bce_logits").data_ptr(), torch.cuda.current_stream().cuda_stream)
-        _native.check(st, "bce_logits_forward")
+        launch("gps_bce_logits_forward", rows, cols, int(x.dtype == torch.bfloat16), x, x.stride(0), int(y.dtype == torch.float32),
+               y, w8, float(scale), partial, loss, _native.ticket(dev, "bce_logits"), device=dev,
+               label=f"bce_logits_forward(rows={rows},cols={cols})", nbytes=nbytes, what="bce_logits_forward")
         ctx.save_for_backward(x, y, *(() if w8 is None else (w8,)))
         ctx.scale = float(scale)
         return loss[0]
@@ -54,14 +50,10 @@ class _BCELogitsSum(torch.autograd.Function):
         rows, cols = x.shape
         g = g.reshape(1).float().contiguous()
         dx = torch.empty((rows, cols), dtype=x.dtype, device=x.device)
-        from ...pointnet2._ext import _timed
         nbytes = 2 * x.numel() * x.element_size() + y.numel() * y.element_size() + (0 if w8 is None else w8.numel())
-        with torch.cuda.device(x.device), _timed(f"bce_logits_backward(rows={rows},cols={cols})", nbytes):
-            st = _native.load().gps_bce_logits_backward(
-                rows, cols, int(x.dtype == torch.bfloat16), x.data_ptr(), x.stride(0), int(y.dtype == torch.float32),
-                y.data_ptr(), None if w8 is None else w8.data_ptr(), ctx.scale, g.data_ptr(), dx.data_ptr(), dx.stride(0),
-                torch.cuda.current_stream().cuda_stream)
-        _native.check(st, "bce_logits_backward")
+        launch("gps_bce_logits_backward", rows, cols, int(x.dtype == torch.bfloat16), x, x.stride(0), int(y.dtype == torch.float32),
+               y, w8, ctx.scale, g, dx, dx.stride(0), device=x.device, label=f"bce_logits_backward(rows={rows},cols={cols})",
+               nbytes=nbytes, what="bce_logits_backward")
         return dx, None, None, None
 
 
@@ -90,13 +82,9 @@ class _TextObjBCE(torch.autograd.Function):
         f = dict(dtype=torch.float32, device=dev)
         cosv, coef, inv_o = torch.empty((B, O), **f), torch.empty((B, O), **f), torch.empty((B, O), **f)
         inv_t, loss_rows, scal = torch.empty(B, **f), torch.empty(B, **f), torch.empty(2, **f)
-        from ...pointnet2._ext import _timed
-        with torch.cuda.device(dev), _timed(f"text_obj_bce_forward(B={B},O={O},D={D})", 4 * (obj.numel() + text.numel())):
-            st = _native.load().gps_text_obj_bce_forward(
-                B, O, D, obj.data_ptr(), text.data_ptr(), labels.data_ptr(), masks.data_ptr(), float(eps),
-                cosv.data_ptr(), coef.data_ptr(), inv_o.data_ptr(), inv_t.data_ptr(), loss_rows.data_ptr(), scal.data_ptr(),
-                _native.ticket(dev, "text_obj_bce").data_ptr(), torch.cuda.current_stream().cuda_stream)
-        _native.check(st, "text_obj_bce_forward")
+        launch("gps_text_obj_bce_forward", B, O, D, obj, text, labels, masks, float(eps), cosv, coef, inv_o, inv_t, loss_rows,
+               scal, _native.ticket(dev, "text_obj_bce"), device=dev, label=f"text_obj_bce_forward(B={B},O={O},D={D})",
+               nbytes=4 * (obj.numel() + text.numel()), what="text_obj_bce_forward")
         ctx.save_for_backward(obj, text, cosv, coef, inv_o, inv_t, scal)
         ctx.eps = float(eps)
         return scal[0]
@@ -108,13 +96,9 @@ class _TextObjBCE(torch.autograd.Function):
         g = g.reshape(1).float().contiguous()
         dobj = torch.empty_like(obj) if ctx.needs_input_grad[0] else None
         dtext = torch.empty_like(text) if ctx.needs_input_grad[1] else None
-        from ...pointnet2._ext import _timed
-        with torch.cuda.device(obj.device), _timed(f"text_obj_bce_backward(B={B},O={O},D={D})", 8 * obj.numel()):
-            st = _native.load().gps_text_obj_bce_backward(
-                B, O, D, obj.data_ptr(), text.data_ptr(), ctx.eps, cosv.data_ptr(), coef.data_ptr(), inv_o.data_ptr(),
-                inv_t.data_ptr(), scal.data_ptr(), g.data_ptr(), dobj.data_ptr() if dobj is not None else None,
-                dtext.data_ptr() if dtext is not None else None, torch.cuda.current_stream().cuda_stream)
-        _native.check(st, "text_obj_bce_backward")
+        launch("gps_text_obj_bce_backward", B, O, D, obj, text, ctx.eps, cosv, coef, inv_o, inv_t, scal, g, dobj, dtext,
+               device=obj.device, label=f"text_obj_bce_backward(B={B},O={O},D={D})", nbytes=8 * obj.numel(),
+               what="text_obj_bce_backward")
         return dobj, dtext, None, None, None
 
 

@@ -9,6 +9,8 @@ from __future__ import annotations
 import torch
 
 from ... import _native
+from ..._launch import launch
+
 
 def _rows_ok(*ts) -> bool:
     return all(t.is_cuda and t.dtype == torch.float32 and t.shape[-1] % 4 == 0 and t.shape[-1] <= 8192 for t in ts)
@@ -25,12 +27,8 @@ class _TextObjCE(torch.autograd.Function):
         f = dict(dtype=torch.float32, device=dev)
         cosv, prob, inv_o = torch.empty((B, O), **f), torch.empty((B, O), **f), torch.empty((B, O), **f)
         inv_t, loss_rows, scal = torch.empty(B, **f), torch.empty(B, **f), torch.empty(2, **f)
-        with torch.cuda.device(dev):
-            st = _native.load().gps_text_obj_ce_forward(
-                B, O, D, obj.data_ptr(), text.data_ptr(), labels.data_ptr(), masks.data_ptr(), float(eps), int(ignore_index),
-                cosv.data_ptr(), prob.data_ptr(), inv_o.data_ptr(), inv_t.data_ptr(), loss_rows.data_ptr(), scal.data_ptr(),
-                _native.ticket(dev, "text_obj").data_ptr(), torch.cuda.current_stream().cuda_stream)
-        _native.check(st, "text_obj_ce_forward")
+        launch("gps_text_obj_ce_forward", B, O, D, obj, text, labels, masks, float(eps), int(ignore_index), cosv, prob, inv_o,
+               inv_t, loss_rows, scal, _native.ticket(dev, "text_obj"), device=dev)
         ctx.save_for_backward(obj, text, labels, cosv, prob, inv_o, inv_t, scal)
         ctx.meta = (float(eps), int(ignore_index))
         return scal[0]
@@ -43,13 +41,8 @@ class _TextObjCE(torch.autograd.Function):
         g = g.reshape(1).float().contiguous()
         dobj = torch.empty_like(obj) if ctx.needs_input_grad[0] else None
         dtext = torch.empty_like(text) if ctx.needs_input_grad[1] else None
-        with torch.cuda.device(obj.device):
-            st = _native.load().gps_text_obj_ce_backward(
-                B, O, D, obj.data_ptr(), text.data_ptr(), labels.data_ptr(), eps, ignore_index, cosv.data_ptr(),
-                prob.data_ptr(), inv_o.data_ptr(), inv_t.data_ptr(), scal.data_ptr(), g.data_ptr(),
-                dobj.data_ptr() if dobj is not None else None, dtext.data_ptr() if dtext is not None else None,
-                torch.cuda.current_stream().cuda_stream)
-        _native.check(st, "text_obj_ce_backward")
+        launch("gps_text_obj_ce_backward", B, O, D, obj, text, labels, eps, ignore_index, cosv, prob, inv_o, inv_t, scal, g,
+               dobj, dtext, device=obj.device)
         return dobj, dtext, None, None, None, None
 
 
@@ -78,12 +71,8 @@ class _ClipLoss(torch.autograd.Function):
         M = torch.empty((n, n), **f)
         lse_row, lse_col, inv_a, inv_b, rows = (torch.empty(n, **f) for _ in range(5))
         loss = torch.empty(1, **f)
-        with torch.cuda.device(dev):
-            st = _native.load().gps_clip_loss_forward(
-                n, D, int(bool(normalize)), a.data_ptr(), b.data_ptr(), scale32.data_ptr(), float(max_scale), float(eps),
-                M.data_ptr(), lse_row.data_ptr(), lse_col.data_ptr(), inv_a.data_ptr(), inv_b.data_ptr(), rows.data_ptr(),
-                loss.data_ptr(), _native.ticket(dev, "clip_fwd").data_ptr(), torch.cuda.current_stream().cuda_stream)
-        _native.check(st, "clip_loss_forward")
+        launch("gps_clip_loss_forward", n, D, int(bool(normalize)), a, b, scale32, float(max_scale), float(eps), M, lse_row,
+               lse_col, inv_a, inv_b, rows, loss, _native.ticket(dev, "clip_fwd"), device=dev)
         ctx.save_for_backward(a, b, scale32, M, lse_row, lse_col, inv_a, inv_b)
         ctx.meta = (bool(normalize), float(max_scale), float(eps), scale.dtype, scale.shape)
         return loss[0]
@@ -99,13 +88,8 @@ class _ClipLoss(torch.autograd.Function):
         db = torch.empty_like(b) if feats else None
         dscale = torch.empty(1, dtype=torch.float32, device=a.device)
         rows = torch.empty(n, dtype=torch.float32, device=a.device)
-        with torch.cuda.device(a.device):
-            st = _native.load().gps_clip_loss_backward(
-                n, D, int(normalize), a.data_ptr(), b.data_ptr(), scale32.data_ptr(), max_scale, eps, M.data_ptr(),
-                lse_row.data_ptr(), lse_col.data_ptr(), inv_a.data_ptr(), inv_b.data_ptr(), g.data_ptr(),
-                da.data_ptr() if feats else None, db.data_ptr() if feats else None, dscale.data_ptr(), rows.data_ptr(),
-                _native.ticket(a.device, "clip_bwd").data_ptr(), torch.cuda.current_stream().cuda_stream)
-        _native.check(st, "clip_loss_backward")
+        launch("gps_clip_loss_backward", n, D, int(normalize), a, b, scale32, max_scale, eps, M, lse_row, lse_col, inv_a, inv_b,
+               g, da, db, dscale, rows, _native.ticket(a.device, "clip_bwd"), device=a.device)
         ds = dscale.reshape(s_shape).to(s_dtype) if ctx.needs_input_grad[2] else None
         return (da if ctx.needs_input_grad[0] else None), (db if ctx.needs_input_grad[1] else None), ds, None, None, None
 

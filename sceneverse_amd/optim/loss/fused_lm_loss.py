@@ -28,7 +28,9 @@ from typing import Optional
 import torch
 
 from ... import _native
+from ..._launch import launch
 from ...modules.layers import gemm as G
+
 
 class HitsSink:
     """Where `_SparseLMLoss.forward` adds its hit counts: `words` = 6 int64 counter words of gps_cls_hits (hits and
@@ -75,10 +77,7 @@ def row_plan(labels: torch.Tensor, vocab: int, ignore_index: int):
     perm = torch.empty(n, dtype=torch.int64, device=labels.device)
     lp = torch.empty(n, dtype=torch.int64, device=labels.device)
     n_valid = torch.empty(1, dtype=torch.int32, device=labels.device)
-    with torch.cuda.device(labels.device):
-        st = _native.load().gps_lm_row_plan(n, int(vocab), labels.data_ptr(), int(ignore_index), perm.data_ptr(),
-                                            lp.data_ptr(), n_valid.data_ptr(), torch.cuda.current_stream().cuda_stream)
-    _native.check(st, "lm_row_plan")
+    launch("gps_lm_row_plan", n, int(vocab), labels, int(ignore_index), perm, lp, n_valid, device=labels.device)
     return perm, lp, n_valid
 
 
@@ -98,11 +97,8 @@ class _PermuteLiveRows(torch.autograd.Function):
             # one launch: dx[perm[r]] = r < *n_valid ? dy[r] : 0 (perm is a bijection: every row of dx is written)
             dy = dy.contiguous()
             dx = torch.empty_like(dy)
-            with torch.cuda.device(dy.device):
-                st = _native.load().gps_rows_move(dy.shape[0], dy.shape[0], dy.shape[0], dy.shape[1] * dy.element_size(),
-                                                  dy.data_ptr(), None, dx.data_ptr(), perm.data_ptr(), n_valid.data_ptr(), 1,
-                                                  torch.cuda.current_stream().cuda_stream)
-            _native.check(st, "rows_move")
+            launch("gps_rows_move", dy.shape[0], dy.shape[0], dy.shape[0], dy.shape[1] * dy.element_size(), dy, None, dx, perm,
+                   n_valid, 1, device=dy.device)
             return dx, None, None
         live = (torch.arange(dy.shape[0], device=dy.device) < n_valid)[:, None]
         dy = torch.where(live, dy, torch.zeros((), dtype=dy.dtype, device=dy.device))
@@ -140,7 +136,6 @@ class _SparseLMLoss(torch.autograd.Function):
         V = weight.shape[0]
         w16, b32 = _padded_shadow(weight, bias)
         Vp = w16.shape[0]
-        lib = _native.load()
         dev = h.device
         if plan is None:
             perm, lp, n_valid = row_plan(labels, V, ignore_index)
@@ -153,11 +148,8 @@ class _SparseLMLoss(torch.autograd.Function):
         rows = torch.empty(n, dtype=torch.float32, device=dev)
         lse = torch.empty(n, dtype=torch.float32, device=dev)
         mean = torch.empty(2, dtype=torch.float32, device=dev)           # [mean over the labelled rows, their number]
-        with torch.cuda.device(dev):
-            st = lib.gps_masked_ce_forward_rows(n, V, 1, logits.data_ptr(), Vp, lp.data_ptr(), int(ignore_index),
-                                                n_valid.data_ptr(), rows.data_ptr(), lse.data_ptr(), mean.data_ptr(),
-                                                _native.ticket(dev, "lm_loss").data_ptr(), torch.cuda.current_stream().cuda_stream)
-        _native.check(st, "masked_ce_forward")
+        launch("gps_masked_ce_forward_rows", n, V, 1, logits, Vp, lp, int(ignore_index), n_valid, rows, lse, mean,
+               _native.ticket(dev, "lm_loss"), device=dev, what="masked_ce_forward")
         sink = _HITS_SINK
         if sink is not None:
             # the masked-LM hit count of the rows just computed: columns [V, Vp) are padding and never candidates
@@ -178,15 +170,11 @@ class _SparseLMLoss(torch.autograd.Function):
         n, D, V, Vp, ignore_index, h_dtype, has_bias = ctx.meta
         lib = _native.load()
         dev = hp.device
-        stream = torch.cuda.current_stream().cuda_stream
         g32 = g.reshape(1).float().contiguous()                             # (no launch for the fp32 scalar autograd hands over)
         dlogits = torch.empty((n, Vp), dtype=torch.bfloat16, device=dev)
-        with torch.cuda.device(dev):
-            # rows past n_valid stay unwritten: the two GEMMs below stop at the extent (their ragged tail reads zeros)
-            st = lib.gps_masked_ce_backward_rows(n, V, 1, logits.data_ptr(), Vp, lp.data_ptr(), ignore_index,
-                                                 n_valid.data_ptr(), lse.data_ptr(), None, g32.data_ptr(),
-                                                 mean[1:].data_ptr(), dlogits.data_ptr(), Vp, stream)
-        _native.check(st, "masked_ce_backward")
+        # rows past n_valid stay unwritten: the two GEMMs below stop at the extent (their ragged tail reads zeros)
+        launch("gps_masked_ce_backward_rows", n, V, 1, logits, Vp, lp, ignore_index, n_valid, lse, None, g32, mean[1:], dlogits, Vp,
+               device=dev, what="masked_ce_backward")
         dh = dw = db = None
         if ctx.needs_input_grad[0]:
             # dX = dlogits . W: a reduction over the vocabulary for a few hundred rows -> split-K into fp32

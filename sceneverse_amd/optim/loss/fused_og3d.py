@@ -9,6 +9,7 @@ from __future__ import annotations
 import torch
 
 from ... import _native
+from ..._launch import launch
 
 MAX_O = 512
 
@@ -28,16 +29,11 @@ class _Og3dCE(torch.autograd.Function):
             x = x.contiguous()
         tgt = target.reshape(B).contiguous()
         dev = x.device
-        lib = _native.load()
         f = dict(dtype=torch.float32, device=dev)
         loss, unit = torch.empty(1, **f), torch.empty((B, O), **f)
-        partial = torch.empty(int(lib.gps_og3d_ce_partial_floats(B)), **f)
-        from ...pointnet2._ext import _timed
-        with torch.cuda.device(dev), _timed(f"og3d_ce_forward(B={B},O={O})", 8 * B * O + 8 * B):
-            st = lib.gps_og3d_ce_forward(B, O, x.data_ptr(), x.stride(0) if B > 1 else O, tgt.data_ptr(), loss.data_ptr(),
-                                         unit.data_ptr(), partial.data_ptr(), _native.ticket(dev, "og3d_ce").data_ptr(),
-                                         torch.cuda.current_stream().cuda_stream)
-        _native.check(st, "og3d_ce_forward")
+        partial = torch.empty(int(_native.load().gps_og3d_ce_partial_floats(B)), **f)
+        launch("gps_og3d_ce_forward", B, O, x, x.stride(0) if B > 1 else O, tgt, loss, unit, partial, _native.ticket(dev, "og3d_ce"),
+               device=dev, label=f"og3d_ce_forward(B={B},O={O})", nbytes=8 * B * O + 8 * B, what="og3d_ce_forward")
         ctx.save_for_backward(unit)
         ctx.dtype = logits.dtype
         return loss[0]

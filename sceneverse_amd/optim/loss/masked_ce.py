@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import torch
 
-from ... import _native
+from ..._launch import launch
 
 
 class _MaskedCE(torch.autograd.Function):
@@ -19,13 +19,8 @@ class _MaskedCE(torch.autograd.Function):
         labels = labels.contiguous().to(torch.int64)
         loss = torch.empty(n, dtype=torch.float32, device=logits.device)
         lse = torch.empty(n, dtype=torch.float32, device=logits.device)
-        from ...pointnet2._ext import _timed
-        with torch.cuda.device(logits.device), _timed("masked_ce_forward", n * v * logits.element_size() // 8):
-            st = _native.load().gps_masked_ce_forward(
-                n, v, int(logits.dtype == torch.bfloat16), logits.data_ptr(), logits.stride(0),
-                labels.data_ptr(), int(ignore_index), loss.data_ptr(), lse.data_ptr(),
-                torch.cuda.current_stream().cuda_stream)
-        _native.check(st, "masked_ce_forward")
+        launch("gps_masked_ce_forward", n, v, int(logits.dtype == torch.bfloat16), logits, logits.stride(0), labels,
+               int(ignore_index), loss, lse, device=logits.device, nbytes=n * v * logits.element_size() // 8)
         ctx.save_for_backward(logits, labels, lse)
         ctx.ignore_index = int(ignore_index)
         return loss
@@ -36,13 +31,9 @@ class _MaskedCE(torch.autograd.Function):
         n, v = logits.shape
         grad_rows = grad_rows.contiguous().float()
         dlogits = torch.empty((n, v), dtype=logits.dtype, device=logits.device)
-        from ...pointnet2._ext import _timed
-        with torch.cuda.device(logits.device), _timed("masked_ce_backward", n * v * logits.element_size()):
-            st = _native.load().gps_masked_ce_backward(
-                n, v, int(logits.dtype == torch.bfloat16), logits.data_ptr(), logits.stride(0),
-                labels.data_ptr(), ctx.ignore_index, lse.data_ptr(), grad_rows.data_ptr(),
-                dlogits.data_ptr(), dlogits.stride(0), torch.cuda.current_stream().cuda_stream)
-        _native.check(st, "masked_ce_backward")
+        launch("gps_masked_ce_backward", n, v, int(logits.dtype == torch.bfloat16), logits, logits.stride(0), labels,
+               ctx.ignore_index, lse, grad_rows, dlogits, dlogits.stride(0), device=logits.device,
+               nbytes=n * v * logits.element_size())
         return dlogits, None, None
 
 

@@ -5,6 +5,7 @@ and return conventions as the host wrappers in sampling.cpp / ball_query.cpp / g
 interpolate.cpp -- but each call goes straight to the C ABI of libgps_hip.so on the current
 torch stream.  GPU tensors only: there is deliberately no CPU path (the reference has none
 either: `AT_ASSERT(false, "CPU not supported")`).
+`profile_start` / `profile_stop` / `profiling` are re-exports of sceneverse_amd/_launch.py, kept under the names callers use.
 """
 from __future__ import annotations
 
@@ -13,66 +14,9 @@ import torch
 from .. import _native
 
 
-def _stream() -> int:
-    return torch.cuda.current_stream().cuda_stream
-
-
-# ---- optional per-launch timing (bench.py): HIP events on the launch stream ------------------
-_PROFILE = None  # None | {op name: [(start_event, end_event, algorithmic_bytes), ...]}
-
-
-def profile_start() -> None:
-    global _PROFILE
-    _PROFILE = {}
-
-
-def profiling() -> bool:
-    return _PROFILE is not None
-
-
-def profile_stop() -> dict:
-    """-> {op: {"launches": n, "avg_us": t, "bytes_per_launch": B, "flops_per_launch": F,
-    "mfma_dtype": "fp32"|"bf16"|None}} (synchronises)."""
-    global _PROFILE
-    rec, _PROFILE = _PROFILE or {}, None
-    torch.cuda.synchronize()
-    out = {}
-    for name, evs in rec.items():
-        ms = [s.elapsed_time(e) for s, e, *_ in evs]
-        # launches with a device-side extent (gps_gemm_args.extent_dev) did only `frac` of the work their static
-        # shape names: the snapshot of the extent word taken at launch time is read back here, once
-        fr = [ev[5]() if ev[5] is not None else 1.0 for ev in evs]
-        out[name] = {"launches": len(evs), "avg_us": 1e3 * sum(ms) / len(ms),
-                     "bytes_per_launch": sum((ev[2](f) if callable(ev[2]) else ev[2] * f) for ev, f in zip(evs, fr)) / len(evs),
-                     "flops_per_launch": sum(ev[3] * f for ev, f in zip(evs, fr)) / len(evs),
-                     "mfma_dtype": evs[0][4]}
-        if any(ev[5] is not None for ev in evs):
-            out[name]["work_fraction"] = sum(fr) / len(fr)
-    return out
-
-
-class _timed:
-    """Brackets one native launch with two events on the current (= launch) stream."""
-
-    def __init__(self, name: str, algo_bytes: int, algo_flops: int = 0, mfma_dtype=None, work_fraction=None):
-        """work_fraction: None, or a callable evaluated at profile_stop() -> the share of the static shape's
-        algorithmic work this launch really did (device-side extents)."""
-        self.name, self.bytes, self.flops, self.mfma = name, algo_bytes, algo_flops, mfma_dtype
-        self.work_fraction = work_fraction
-
-    def __enter__(self):
-        if _PROFILE is not None:
-            self.s = torch.cuda.Event(enable_timing=True)
-            self.e = torch.cuda.Event(enable_timing=True)
-            self.s.record()
-        return self
-
-    def __exit__(self, *exc):
-        if _PROFILE is not None:
-            self.e.record()
-            _PROFILE.setdefault(self.name, []).append((self.s, self.e, self.bytes, self.flops, self.mfma,
-                                                       self.work_fraction))
-        return False
+# the per-launch profile lives with the launch itself (sceneverse_amd/_launch.py); re-exported under the names
+# bench.py and the tests call
+from .._launch import launch, profile_start, profile_stop, profiling  # noqa: F401
 
 
 def _chk(t: torch.Tensor, name: str, dtype: torch.dtype) -> None:
@@ -98,10 +42,8 @@ def gather_points(points: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     b, c, n = points.shape
     m = idx.shape[1]
     out = torch.empty((b, c, m), dtype=torch.float32, device=points.device)
-    with torch.cuda.device(points.device), _timed("gather_points", 4 * (b * m + 2 * b * c * m)):   # idx + gathered elements read, output written
-        st = _native.load().gps_gather_points(b, c, n, m, points.data_ptr(), idx.data_ptr(),
-                                              out.data_ptr(), _stream())
-    _native.check(st, "gather_points")
+    launch("gps_gather_points", b, c, n, m, points, idx, out, device=points.device,
+           nbytes=4 * (b * m + 2 * b * c * m))   # idx + gathered elements read, output written
     return out
 
 
@@ -111,10 +53,8 @@ def gather_points_grad(grad_out: torch.Tensor, idx: torch.Tensor, n: int) -> tor
     _same_device(grad_out, idx)
     b, c, m = grad_out.shape
     out = torch.empty((b, c, int(n)), dtype=torch.float32, device=grad_out.device)
-    with torch.cuda.device(grad_out.device), _timed("gather_points_grad", 4 * (b * c * m + b * m + b * c * int(n))):
-        st = _native.load().gps_gather_points_grad(b, c, int(n), m, grad_out.data_ptr(),
-                                                   idx.data_ptr(), out.data_ptr(), _stream())
-    _native.check(st, "gather_points_grad")
+    launch("gps_gather_points_grad", b, c, int(n), m, grad_out, idx, out, device=grad_out.device,
+           nbytes=4 * (b * c * m + b * m + b * c * int(n)))
     return out
 
 
@@ -126,11 +66,8 @@ def furthest_point_sampling(points: torch.Tensor, nsamples: int) -> torch.Tensor
     temp = None
     if n > 2048:  # GPS_FPS_MAX_RESIDENT_N: streaming form keeps running distances in HBM
         temp = torch.empty((b, n), dtype=torch.float32, device=points.device)
-    with torch.cuda.device(points.device), _timed(f"furthest_point_sampling(n={n},m={m})", 4 * (b * n * 3 + b * m)):
-        st = _native.load().gps_furthest_point_sampling(
-            b, n, m, points.data_ptr(), temp.data_ptr() if temp is not None else None,
-            out.data_ptr(), _stream())
-    _native.check(st, "furthest_point_sampling")
+    launch("gps_furthest_point_sampling", b, n, m, points, temp, out, device=points.device,
+           label=f"furthest_point_sampling(n={n},m={m})", nbytes=4 * (b * n * 3 + b * m), what="furthest_point_sampling")
     return out
 
 
@@ -144,10 +81,9 @@ def furthest_point_sampling_xyz(points: torch.Tensor, nsamples: int):
         return None
     out = torch.empty((b, m), dtype=torch.int32, device=points.device)
     cen = torch.empty((b, m, 3), dtype=torch.float32, device=points.device)
-    with torch.cuda.device(points.device), _timed(f"furthest_point_sampling(n={n},m={m})", 4 * (b * n * 3 + b * m * 4)):
-        st = _native.load().gps_furthest_point_sampling_xyz(b, n, m, points.data_ptr(), out.data_ptr(), cen.data_ptr(),
-                                                            _stream())
-    _native.check(st, "furthest_point_sampling_xyz")
+    launch("gps_furthest_point_sampling_xyz", b, n, m, points, out, cen, device=points.device,
+           label=f"furthest_point_sampling(n={n},m={m})", nbytes=4 * (b * n * 3 + b * m * 4),
+           what="furthest_point_sampling_xyz")
     return out, cen
 
 
@@ -169,11 +105,9 @@ def cloud_compact(cloud: torch.Tensor, rows_mult: int = 16) -> CloudPlan:
     plan.slot_of = torch.empty(b, dtype=torch.int64, device=dev)
     plan.scal = torch.empty(4, dtype=torch.int32, device=dev)
     flag = torch.empty(2 * b, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev), _timed(f"cloud_compact(n={n},ld={ld})", 4 * b * n * ld * 2):
-        st = _native.load().gps_cloud_compact(b, n, ld, cloud.data_ptr(), int(rows_mult), flag.data_ptr(), plan.obj_of.data_ptr(),
-                                              plan.slot_of.data_ptr(), plan.scal.data_ptr(), plan.xyz.data_ptr(),
-                                              plan.feats_pm.data_ptr() if ld > 3 else None, _stream())
-    _native.check(st, "cloud_compact")
+    launch("gps_cloud_compact", b, n, ld, cloud, int(rows_mult), flag, plan.obj_of, plan.slot_of, plan.scal, plan.xyz,
+           plan.feats_pm if ld > 3 else None, device=dev, label=f"cloud_compact(n={n},ld={ld})", nbytes=4 * b * n * ld * 2,
+           what="cloud_compact")
     plan.n_work, plan.rows16 = plan.scal[0:1], plan.scal[3:4]
     return plan
 
@@ -201,10 +135,8 @@ def three_nn(unknowns: torch.Tensor, knows: torch.Tensor):
     m = knows.shape[1]
     dist2 = torch.empty((b, n, 3), dtype=torch.float32, device=unknowns.device)
     idx = torch.empty((b, n, 3), dtype=torch.int32, device=unknowns.device)
-    with torch.cuda.device(unknowns.device), _timed("three_nn", 4 * (b * n * 3 + b * m * 3 + 2 * b * n * 3)):
-        st = _native.load().gps_three_nn(b, n, m, unknowns.data_ptr(), knows.data_ptr(),
-                                         dist2.data_ptr(), idx.data_ptr(), _stream())
-    _native.check(st, "three_nn")
+    launch("gps_three_nn", b, n, m, unknowns, knows, dist2, idx, device=unknowns.device,
+           nbytes=4 * (b * n * 3 + b * m * 3 + 2 * b * n * 3))
     return [dist2, idx]
 
 
@@ -216,10 +148,8 @@ def three_interpolate(points: torch.Tensor, idx: torch.Tensor, weight: torch.Ten
     b, c, m = points.shape
     n = idx.shape[1]
     out = torch.empty((b, c, n), dtype=torch.float32, device=points.device)
-    with torch.cuda.device(points.device), _timed("three_interpolate", 4 * (b * c * m + 2 * b * n * 3 + b * c * n)):
-        st = _native.load().gps_three_interpolate(b, c, m, n, points.data_ptr(), idx.data_ptr(),
-                                                  weight.data_ptr(), out.data_ptr(), _stream())
-    _native.check(st, "three_interpolate")
+    launch("gps_three_interpolate", b, c, m, n, points, idx, weight, out, device=points.device,
+           nbytes=4 * (b * c * m + 2 * b * n * 3 + b * c * n))
     return out
 
 
@@ -231,11 +161,8 @@ def three_interpolate_grad(grad_out: torch.Tensor, idx: torch.Tensor, weight: to
     _same_device(grad_out, idx, weight)
     b, c, n = grad_out.shape
     out = torch.empty((b, c, int(m)), dtype=torch.float32, device=grad_out.device)
-    with torch.cuda.device(grad_out.device), _timed("three_interpolate_grad", 4 * (b * c * n + 2 * b * n * 3 + b * c * int(m))):
-        st = _native.load().gps_three_interpolate_grad(b, c, n, int(m), grad_out.data_ptr(),
-                                                       idx.data_ptr(), weight.data_ptr(),
-                                                       out.data_ptr(), _stream())
-    _native.check(st, "three_interpolate_grad")
+    launch("gps_three_interpolate_grad", b, c, n, int(m), grad_out, idx, weight, out, device=grad_out.device,
+           nbytes=4 * (b * c * n + 2 * b * n * 3 + b * c * int(m)))
     return out
 
 
@@ -246,11 +173,9 @@ def ball_query(new_xyz: torch.Tensor, xyz: torch.Tensor, radius: float, nsample:
     b, m, _ = new_xyz.shape
     n = xyz.shape[1]
     idx = torch.empty((b, m, int(nsample)), dtype=torch.int32, device=new_xyz.device)
-    with torch.cuda.device(new_xyz.device), _timed(f"ball_query(n={n},m={m},ns={int(nsample)})", 4 * (b * (n + m) * 3 + b * m * int(nsample))):
-        st = _native.load().gps_ball_query(b, n, m, float(radius), int(nsample),
-                                           new_xyz.data_ptr(), xyz.data_ptr(), idx.data_ptr(),
-                                           _stream())
-    _native.check(st, "ball_query")
+    launch("gps_ball_query", b, n, m, float(radius), int(nsample), new_xyz, xyz, idx, device=new_xyz.device,
+           label=f"ball_query(n={n},m={m},ns={int(nsample)})", nbytes=4 * (b * (n + m) * 3 + b * m * int(nsample)),
+           what="ball_query")
     return idx
 
 
@@ -261,10 +186,9 @@ def group_points(points: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     b, c, n = points.shape
     _, npoints, nsample = idx.shape
     out = torch.empty((b, c, npoints, nsample), dtype=torch.float32, device=points.device)
-    with torch.cuda.device(points.device), _timed(f"group_points(c={c},n={n},np={npoints},ns={nsample})", 4 * (b * c * n + b * npoints * nsample + b * c * npoints * nsample)):
-        st = _native.load().gps_group_points(b, c, n, npoints, nsample, points.data_ptr(),
-                                             idx.data_ptr(), out.data_ptr(), _stream())
-    _native.check(st, "group_points")
+    launch("gps_group_points", b, c, n, npoints, nsample, points, idx, out, device=points.device,
+           label=f"group_points(c={c},n={n},np={npoints},ns={nsample})",
+           nbytes=4 * (b * c * n + b * npoints * nsample + b * c * npoints * nsample), what="group_points")
     return out
 
 
@@ -274,11 +198,9 @@ def group_points_grad(grad_out: torch.Tensor, idx: torch.Tensor, n: int) -> torc
     _same_device(grad_out, idx)
     b, c, npoints, nsample = grad_out.shape
     out = torch.empty((b, c, int(n)), dtype=torch.float32, device=grad_out.device)
-    with torch.cuda.device(grad_out.device), _timed(f"group_points_grad(c={c},n={int(n)},np={npoints},ns={nsample})", 4 * (b * c * npoints * nsample + b * npoints * nsample + b * c * int(n))):
-        st = _native.load().gps_group_points_grad(b, c, int(n), npoints, nsample,
-                                                  grad_out.data_ptr(), idx.data_ptr(),
-                                                  out.data_ptr(), _stream())
-    _native.check(st, "group_points_grad")
+    launch("gps_group_points_grad", b, c, int(n), npoints, nsample, grad_out, idx, out, device=grad_out.device,
+           label=f"group_points_grad(c={c},n={int(n)},np={npoints},ns={nsample})",
+           nbytes=4 * (b * c * npoints * nsample + b * npoints * nsample + b * c * int(n)), what="group_points_grad")
     return out
 
 
@@ -301,7 +223,7 @@ def sa_mlp_pack(weights, shifts, precision: str = "fp32") -> torch.Tensor:
     assert precision in SA_PRECISIONS, precision
     x3 = precision == "bf16x3"
     layer_floats = lib.gps_sa_mlp_layer_floats_bf16x3 if x3 else lib.gps_sa_mlp_layer_floats
-    pack_layer = lib.gps_sa_mlp_pack_layer_bf16x3 if x3 else lib.gps_sa_mlp_pack_layer
+    pack_layer = "gps_sa_mlp_pack_layer_bf16x3" if x3 else "gps_sa_mlp_pack_layer"
     sizes = []
     for w in weights:
         n = int(layer_floats(w.shape[1], w.shape[0]))
@@ -310,15 +232,13 @@ def sa_mlp_pack(weights, shifts, precision: str = "fp32") -> torch.Tensor:
         sizes.append(n)
     buf = torch.empty(sum(sizes), dtype=torch.float32, device=weights[0].device)
     off = 0
-    with torch.cuda.device(buf.device):
-        for w, sft, n in zip(weights, shifts, sizes):
-            w, sft = w.contiguous(), sft.contiguous()
-            _chk(w, "weight", torch.float32)
-            _chk(sft, "shift", torch.float32)
-            st = pack_layer(w.shape[1], w.shape[0], w.data_ptr(), sft.data_ptr(),
-                            buf.data_ptr() + 4 * off, _stream())
-            _native.check(st, "sa_mlp_pack_layer")
-            off += n
+    for w, sft, n in zip(weights, shifts, sizes):
+        w, sft = w.contiguous(), sft.contiguous()
+        _chk(w, "weight", torch.float32)
+        _chk(sft, "shift", torch.float32)
+        launch(pack_layer, w.shape[1], w.shape[0], w, sft, buf.data_ptr() + 4 * off, device=buf.device,
+               what="sa_mlp_pack_layer")
+        off += n
     return buf
 
 
@@ -358,12 +278,9 @@ def sa_mlp_forward(xyz: torch.Tensor, new_xyz: torch.Tensor, features: torch.Ten
         out = torch.empty((b, c3, npoint), dtype=torch.float32, device=xyz.device)
         algo = 4 * (b * 3 * n + b * 3 * npoint + b * c_feat * n + b * npoint * nsample + b * c3 * npoint)
         flops = 2 * b * npoint * nsample * ((3 + c_feat) * c1 + c1 * c2 + c2 * c3)      # dense count: see below
-        with torch.cuda.device(xyz.device), _timed(f"sa_mlp_forward(c={c_feat},n={n},np={npoint},mlp={c1}-{c2}-{c3},{precision})",
-                                                    algo, 3 * flops, "bf16"):
-            st = _native.load().gps_sa_mlp_forward_bf16x3_pm(b, n, npoint, nsample, c_feat, c1, c2, c3, xyz.data_ptr(),
-                                                             new_xyz.data_ptr(), features.data_ptr(), ld_feat, idx.data_ptr(),
-                                                             wpack.data_ptr(), out.data_ptr(), _stream())
-        _native.check(st, "sa_mlp_forward_pm")
+        launch("gps_sa_mlp_forward_bf16x3_pm", b, n, npoint, nsample, c_feat, c1, c2, c3, xyz, new_xyz, features, ld_feat, idx,
+               wpack, out, device=xyz.device, label=f"sa_mlp_forward(c={c_feat},n={n},np={npoint},mlp={c1}-{c2}-{c3},{precision})",
+               nbytes=algo, flops=3 * flops, mfma="bf16", what="sa_mlp_forward_pm")
         return out
     _chk(features, "features", torch.float32)
     _same_device(xyz, new_xyz, features, idx, wpack)
@@ -381,11 +298,8 @@ def sa_mlp_forward(xyz: torch.Tensor, new_xyz: torch.Tensor, features: torch.Ten
     # so flops / time over the MFMA peak is a roof fraction of the algorithm, NOT the occupancy of the matrix pipe.
     flops = 2 * b * npoint * nsample * ((3 + c_feat) * c1 + c1 * c2 + c2 * c3)
     x3 = precision == "bf16x3"
-    fn = _native.load().gps_sa_mlp_forward_bf16x3 if x3 else _native.load().gps_sa_mlp_forward
-    with torch.cuda.device(xyz.device), _timed(f"sa_mlp_forward(c={c_feat},n={n},np={npoint},mlp={c1}-{c2}-{c3},{precision})",
-                                                algo, 3 * flops if x3 else flops, "bf16" if x3 else "fp32"):
-        st = fn(b, n, npoint, nsample, c_feat, c1, c2, c3,
-                                               xyz.data_ptr(), new_xyz.data_ptr(), features.data_ptr(),
-                                               idx.data_ptr(), wpack.data_ptr(), out.data_ptr(), _stream())
-    _native.check(st, "sa_mlp_forward")
+    launch("gps_sa_mlp_forward_bf16x3" if x3 else "gps_sa_mlp_forward", b, n, npoint, nsample, c_feat, c1, c2, c3, xyz, new_xyz,
+           features, idx, wpack, out, device=xyz.device,
+           label=f"sa_mlp_forward(c={c_feat},n={n},np={npoint},mlp={c1}-{c2}-{c3},{precision})", nbytes=algo,
+           flops=3 * flops if x3 else flops, mfma="bf16" if x3 else "fp32", what="sa_mlp_forward")
     return out
