@@ -262,8 +262,13 @@ GPS_API void gps_attn_set_stream_min_tiles(int plain, int spatial);
  *   4  fixed-length self-attention up to 144 tokens on the K / V-resident kernels of gps_attention_sp.hip (one query strip
  *      per wave, probabilities and dS parked in LDS for the dK / dV pass: every score evaluated once).  Plain form only:
  *      the spatial form's plane kernels (gps_attn_args.pl_planes, up to 512 rows) do not depend on this mask.
- * Calls no set bit covers take the whole-sequence kernels of gps_attention.hip.  Default 1 | 4 (measured, profiles/r5:
- * the block-streaming backward ties the whole-sequence one on the variable-length text batches).  All families share lse
+ *   8  backward calls of self-attention (Lq = Lk, fixed-length or variable-length batches) up to 320 tokens on the
+ *      one-launch kernel of gps_attention_fa.hip: a workgroup owns a whole (sequence, head), every score, probability
+ *      and dS element is formed once (five products), dQ accumulates in registers over the key blocks; needs `out`, no
+ *      workspace, no atomics (bit-reproducible).  Bit 4 goes first where both apply.
+ * Calls no set bit covers take the whole-sequence kernels of gps_attention.hip.  Default 1 | 4 | 8 (measured:
+ * profiles/r5 -- the two-launch block-streaming backward ties the whole-sequence one on the variable-length text
+ * batches; profiles/attn_bwd_fused -- the one-launch backward against the whole-sequence one).  All families share lse
  * and the dropout stream, so forward and backward may come from different ones.  mode < 0 = query.  Returns the previous
  * mode.  Process-wide. */
 GPS_API int gps_attn_set_plain_blocks(int mode);

@@ -1235,10 +1235,11 @@ int launch(const Params &P, bool backward, hipStream_t s) {
 
 static int g_stream_min_nt[2] = {-1, -1};      // [plain, spatial]; -1 = not read yet
 // plain form (no pairwise term), bits: 1 = forward on the block-streaming kernels of gps_attention_fa.hip, 2 = backward
-// on them too, 4 = fixed-length self-attention up to 144 tokens on the K / V-resident kernels of gps_attention_sp.hip
+// on them too, 4 = fixed-length self-attention up to 144 tokens on the K / V-resident kernels of gps_attention_sp.hip,
+// 8 = backward of self-attention up to 320 tokens on the one-launch kernel of gps_attention_fa.hip
 static int g_plain_mode = [] {
   const char *e = getenv("GPS_ATTN_PLAIN_MODE");            // A/B runs of whole bench commands
-  return e ? (atoi(e) & 7) : (1 | 4);
+  return e ? (atoi(e) & 15) : (1 | 4 | 8);
 }();
 
 int dispatch(Params &P, bool backward, hipStream_t s) {
@@ -1306,12 +1307,15 @@ int run_ex(const gps_attn_args *a, bool backward, hipStream_t s) {
   if ((a->ld_q & 7) || (a->ld_kv & 7) || (a->ld_o & 7) || (backward && ((a->ld_dq & 7) || (a->ld_dkv & 7)))) return GPS_ERR_UNSUPPORTED;
   if (a->compute == GPS_ATTN_COMPUTE_FP8 && !backward) return run_fp8_forward(a, s);
   if (a->compute != GPS_ATTN_COMPUTE_NATIVE && a->compute != GPS_ATTN_COMPUTE_FP8) return GPS_ERR_UNSUPPORTED;
-  // plain form: K / V-resident kernels for short fixed-length rows, block-streaming kernels otherwise (their backward
-  // call needs the forward output and the delta scratch), else the whole-sequence kernels below
+  // plain form: K / V-resident kernels for short fixed-length rows, the one-launch backward for self-attention up to 320
+  // tokens (needs the forward output), block-streaming kernels otherwise (their backward call needs the forward output
+  // and the delta scratch), else the whole-sequence kernels below
   if (!a->sw) {
     if ((g_plain_mode & 4) && a->Lq == a->Lk && a->Lk <= 144 && !a->cu_rows && a->ld_q == a->ld_kv && (!backward || a->ld_dq == a->ld_dkv) &&
         !(a->ld_o & 3) && (!backward || !(a->ld_dq & 3)))
       return run_plain_resident(a, backward, s);
+    if (backward && (g_plain_mode & 8) && a->compute == GPS_ATTN_COMPUTE_NATIVE && a->Lq == a->Lk && a->Lk <= 320 && a->out)
+      return run_plain_fused_bwd(a, s);
     if (!backward ? (g_plain_mode & 1) : ((g_plain_mode & 2) && a->out && a->delta_ws)) return run_plain_blocks(a, backward, s);
   }
   Params P = {};
@@ -1345,7 +1349,7 @@ int gps_attn_backward_ex(const gps_attn_args *a, gps_stream_t stream) {
 
 int gps_attn_set_plain_blocks(int mode) {
   const int was = gps_attn::g_plain_mode;
-  if (mode >= 0) gps_attn::g_plain_mode = mode & 7;
+  if (mode >= 0) gps_attn::g_plain_mode = mode & 15;
   return was;
 }
 

@@ -12,5 +12,6 @@ int run_fp8_forward(const gps_attn_args *a, hipStream_t s);             // gps_a
 int run_spatial_planes(const gps_attn_args *a, bool backward, hipStream_t s);   // gps_attention_sp.hip
 int run_spatial_planes_long(const gps_attn_args *a, bool backward, hipStream_t s);   // gps_attention_spl.hip (L > 144)
 int run_plain_blocks(const gps_attn_args *a, bool backward, hipStream_t s);     // gps_attention_fa.hip
+int run_plain_fused_bwd(const gps_attn_args *a, hipStream_t s);                 // gps_attention_fa.hip (one launch)
 int run_plain_resident(const gps_attn_args *a, bool backward, hipStream_t s);   // gps_attention_sp.hip
 }  // namespace gps_attn

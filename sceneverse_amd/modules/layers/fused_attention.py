@@ -285,13 +285,13 @@ def _delta_ws(n_seq: int, n_head: int, cap: int, device) -> torch.Tensor:
     return torch.empty((n_seq, n_head, cap), dtype=torch.float32, device=device)
 
 
-PLAIN_DEFAULT = 1 | 4
+PLAIN_DEFAULT = 1 | 4 | 8
 
 
 def set_plain_mode(mode: int = PLAIN_DEFAULT) -> int:
     """Kernel families of the plain form (include/gps_hip.h gps_attn_set_plain_blocks): bit 1 = block-streaming forward,
-    2 = block-streaming backward, 4 = K / V-resident kernels for fixed-length rows up to 144 tokens; 0 = the
-    whole-sequence kernels for everything.  Returns the previous mode."""
+    2 = block-streaming backward, 4 = K / V-resident kernels for fixed-length rows up to 144 tokens, 8 = one-launch
+    backward for self-attention up to 320 tokens; 0 = the whole-sequence kernels for everything.  Returns the previous mode."""
     return int(_native.load().gps_attn_set_plain_blocks(int(mode)))
 
 

@@ -5,8 +5,14 @@ forward and backward, GPU time per launch from a replayed HIP graph of `iters` l
   joint     (B, 130) plain form with a key-padding mask (unified encoder): block-streaming vs whole-sequence kernels
   text      128 variable-length sequences packed back to back (64 sentences <= 50, 64 captions <= 300 tokens): the same
 
+  bwd_ab    the step's two plain self-attention BACKWARD launches -- text (128 packed sequences, capacity 300, with and
+            without the last layer's query limit) and joint (64 compacted sequences, capacity 130), p = 0.1 -- in the
+            plain modes of --modes (default 5 = whole-sequence backward, 13 = one-launch backward), alternating,
+            --repeats times; each figure one HIP-graph replay of --iters backward calls (no forward, no autograd)
+
 Checks each new path against the one it replaces (max |diff| relative to max |ref|) before timing it.
     python tools/attn_bench.py [--json out.json] [--iters 20]
+    python tools/attn_bench.py --only bwd_ab --modes 5,13 --repeats 4 --iters 50
 GPS_ATTN_SP_BWD_OCC=3|4 selects the register budget of the spatial backward kernel (process-wide)."""
 import argparse
 import faulthandler
@@ -153,12 +159,62 @@ def text_case(iters, full=False):
     return res
 
 
+def bwd_ab_case(modes, repeats, iters):
+    from kernel_bench import timeit as graph_timeit
+
+    class Ctx:                    # what the autograd Function's forward / backward use of their ctx
+        def save_for_backward(self, *tensors):
+            self.saved_tensors = tensors
+    g = torch.Generator().manual_seed(42)
+    sent, capt = torch.randint(6, 51, (64,), generator=g), torch.randint(30, 301, (64,), generator=g)
+    objs = torch.randint(20, 80, (64,), generator=g)                  # live objects of a scene: data/synthetic.synth_batch
+    text_lens = torch.cat([sent, capt])
+    text_limit = text_lens.clone().to(torch.int32)
+    text_limit[64:] = 1                                               # the last BERT layer reads the captions' first row only
+    shapes = [("text", text_lens, 300, None), ("text_qlimit", text_lens, 300, text_limit), ("joint", sent + objs, 130, None)]
+    seed_dev = FA._next_device_seed(torch.device(DEV))
+    res = {}
+    for name, lens, cap, limit in shapes:
+        n_seq = lens.numel()
+        cu = torch.zeros(n_seq + 1, dtype=torch.int32)
+        cu[1:] = torch.cumsum(lens, 0)
+        T = int(cu[-1])
+        order = torch.argsort(lens, descending=True).to(torch.int32).to(DEV)
+        packed = torch.randn(T, 3 * D, generator=g).to(torch.bfloat16).to(DEV)
+        go = torch.randn(T, D, generator=g).to(torch.bfloat16).to(DEV)
+        cu, limit = cu.to(DEV), (None if limit is None else limit.to(DEV))
+        with torch.no_grad():
+            FA.set_plain_mode(modes[0])
+            ctx = Ctx()
+            FA._FusedVarlenSelfAttention.forward(ctx, packed, cu, n_seq, cap, H, 0.1, seed_dev, order, limit)
+        row = {"rows": T, "sum_len_sq": int((lens.double() ** 2).sum()), "us": {str(m): [] for m in modes}}
+        grads = {}
+        try:
+            for _ in range(repeats):
+                for m in modes:
+                    FA.set_plain_mode(m)
+                    row["us"][str(m)].append(round(graph_timeit(lambda: FA._FusedVarlenSelfAttention.backward(ctx, go), iters=iters), 2))
+            for m in modes:
+                FA.set_plain_mode(m)
+                grads[m] = FA._FusedVarlenSelfAttention.backward(ctx, go)[0]
+            torch.cuda.synchronize()
+        finally:
+            FA.set_plain_mode()
+        for m in modes[1:]:
+            row[f"grad_{m}_vs_{modes[0]}"] = rel(grads[m], grads[modes[0]])
+        res[name] = row
+        print(" ", name, row, flush=True)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--json", default=None)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--only", default="")
+    ap.add_argument("--modes", default="5,13", help="bwd_ab: plain modes to alternate (the first is the reference)")
+    ap.add_argument("--repeats", type=int, default=4, help="bwd_ab: alternating repeats per mode")
     args = ap.parse_args()
     out = {"bwd_occ_env": os.environ.get("GPS_ATTN_SP_BWD_OCC", "")}
     if os.environ.get("GPS_BENCH_WARM"):
@@ -167,7 +223,8 @@ def main():
              ("spatial_L130", lambda: spatial_case(8, 130, args.iters)),
              ("joint_L130", lambda: joint_case(args.batch, 130, args.iters)),
              ("text_varlen", lambda: text_case(args.iters)),
-             ("text_full", lambda: text_case(args.iters, full=True))]
+             ("text_full", lambda: text_case(args.iters, full=True)),
+             ("bwd_ab", lambda: bwd_ab_case([int(m) for m in args.modes.split(",")], args.repeats, args.iters))]
     for name, fn in cases:
         if args.only and not name.startswith(args.only):
             continue
