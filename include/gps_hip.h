@@ -736,6 +736,48 @@ GPS_API int gps_refer_metrics(int B, int O, const void *og3d_logits, long long l
                               const int64_t *iou25, const int64_t *iou50, const int64_t *tgt_id,
                               const uint8_t *is_multiple, int64_t *counters, gps_stream_t stream);
 
+/* ---- resident text batches: token gather, caption / sentence merge, masked-LM and masked-object draws ----
+ * Replaces, per batch and in ONE launch (no atomics, no workspace, no host sync; capturable), the per-sample text work
+ * of MaskDatasetWrapper.__getitem__ (data/datasets/dataset_wrapper.py:38-111: tokenizer(sentence), tokenizer(scene_cap +
+ * " " + sentence), the masking calls), merge_tokens (data/data_utils.py:50-60), random_word (data/data_utils.py:76-104)
+ * and random_point_cloud (data/data_utils.py:107-121).  The corpus is tokenised ONCE by the caller and kept on the device.
+ *   tok (n_tok) int32: the token ids of all texts WITHOUT special tokens; off (n_texts + 1) int64 CSR offsets into it.
+ *   sent_idx (n_rows) int32: text id of each row's sentence; cap_idx (n_rows) int32 caption text id, or NULL = no scene
+ *   outputs.  A text id outside [0, n_texts) (or offsets that leave tok) reads as an empty text.
+ *   L = max_seq_len, Ls = max_scene_cap_len, both >= 2; cls_id, sep_id, mask_id, pad_id, vocab_size: 101, 102, 103, 0,
+ *   30522 for BERT.  obj_masks (n_obj_rows, O) u8 (nonzero = the slot holds an object); n_obj_rows may differ from
+ *   n_rows (B scenes x S sentences), and may be 0 with obj_masks and obj_sem_masks NULL.
+ *   Outputs, every element written: txt_ids, txt_masks, masked_lm_labels (n_rows, L) int64 (masked_lm_labels may be
+ *   NULL when do_mask == 0); scene_txt_ids, scene_txt_masks (n_rows, Ls) int64, given iff cap_idx is;
+ *   obj_sem_masks (n_obj_rows, O) u8 0 / 1.
+ * Sentence: s = the row's tokens, n = min(len(s), L - 2): txt = [cls] s[:n] [sep] then pad_id, txt_masks[t] = t < n + 2.
+ * Scene text: c = the caption's tokens, s' = s[:min(len(s), scene_sent_cap)], body = (c ++ s')[:Ls - 2]:
+ *   scene = [cls] body [sep] then pad_id, mask likewise; never masked.  scene_sent_cap = L - 2 is merge_tokens over an
+ *   already truncated sentence, a very large one is the wrapper's string form (WordPiece splits on whitespace, so the
+ *   tokens of the concatenation are the concatenation of the tokens).
+ * do_mask == 0 (ScanFamilyDatasetWrapperOld): txt_ids unmasked, masked_lm_labels all -1, obj_sem_masks = obj_masks.
+ * do_mask != 0, replay draws given -- u_tok (n_rows, L) f64, rand_tok (n_rows, L) int32, u_obj (n_obj_rows, O) f64, all
+ *   or none (u_obj is not needed without object slots): the reference's own arithmetic in double.  Every position with
+ *   txt_masks == 1 takes part, [CLS] and [SEP] included: p = u_tok[r][t]; p < txt_mask_ratio: label = the id, q = p /
+ *   txt_mask_ratio, q < 0.8 -> mask_id, q < 0.9 -> rand_tok[r][t], else the id stays; otherwise label -1 (pads too).
+ *   obj_sem_masks = obj_masks && !(u_obj < pc_mask_ratio).
+ * do_mask != 0, no replay draws -- the device law, all in integers: S = seed + (seed_dev ? *seed_dev : 0) (csrc/
+ *   gps_dropout.h), T(x) = floor(x * 2^32) as a 64-bit number (2^32 at x = 1: every position).  Token (r, t) draws
+ *   u = rng_u32(S, r * L + t) and is masked iff u < T(txt_mask_ratio); among the masked, 10 u < 8 T -> mask_id,
+ *   8 T <= 10 u < 9 T -> the id (uint64(rng_u32(S + 1, r * L + t)) * vocab_size) >> 32, else the id stays.  Object
+ *   (r, o) is dropped iff rng_u32(S + 2, r * O + o) < T(pc_mask_ratio).
+ * GPS_ERR_INVALID_ARGUMENT: L < 2 or Ls < 2, a negative count or scene_sent_cap, a ratio outside [0, 1], vocab_size < 1,
+ * a NULL mandatory pointer, replay draws or scene outputs given in part.  L, Ls or O above 2^20: GPS_ERR_UNSUPPORTED.
+ * n_rows == 0 (and no object slots): GPS_OK, nothing launched. */
+GPS_API int gps_text_batch(int n_texts, long long n_tok, const int32_t *tok, const int64_t *off, int n_rows,
+                           const int32_t *sent_idx, const int32_t *cap_idx, int L, int Ls, int scene_sent_cap,
+                           int cls_id, int sep_id, int mask_id, int pad_id, int vocab_size, int do_mask,
+                           double txt_mask_ratio, double pc_mask_ratio, int n_obj_rows, int O,
+                           const uint8_t *obj_masks, const double *u_tok, const int32_t *rand_tok,
+                           const double *u_obj, uint64_t seed, const uint64_t *seed_dev, int64_t *txt_ids,
+                           int64_t *txt_masks, int64_t *masked_lm_labels, int64_t *scene_txt_ids,
+                           int64_t *scene_txt_masks, uint8_t *obj_sem_masks, gps_stream_t stream);
+
 /* ---- accuracy counters of the pre-train, ReferIt3D and object-class evaluators -------------------------
  * Replaces the arg-max / compare / sum / `.item()` chains of PretrainEval.batch_metrics (evaluator/pretrain_eval.py:21-67),
  * ReferIt3DEval.batch_metrics (evaluator/referit3d_eval.py:14-83) and PretrainObjEval.batch_metrics

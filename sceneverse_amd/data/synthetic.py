@@ -120,6 +120,22 @@ def synth_qa_batch(batch: int, n_obj: int = 80, n_pts: int = 1024, txt_len: int 
     return {k: v.to(device) for k, v in d.items()}
 
 
+def synth_packed_texts(n_sent: int, n_cap: int, seed: int = 42, device: str | torch.device = "cpu", txt_len: int = 50,
+                       scene_txt_len: int = 300):
+    """A tokenised corpus for `data.gpu_text`: n_sent sentences (text ids 0 .. n_sent - 1) followed by n_cap scene
+    captions (ids n_sent .. n_sent + n_cap - 1), WITHOUT special tokens, with the length laws of `_tokens` above: a
+    sentence has U{6..txt_len} - 2 tokens, a caption U{30..scene_txt_len} - 2, ids ~ U{1000..30521}.
+    -> the finalized PackedTexts on `device`."""
+    from .gpu_text import PackedTexts
+    rng = np.random.default_rng(seed)
+    texts = PackedTexts(device)
+    for n_texts, max_len, min_len in ((n_sent, txt_len, 6), (n_cap, scene_txt_len, min(30, scene_txt_len))):
+        for _ in range(n_texts):
+            n = int(rng.integers(min(min_len, max_len), max_len + 1))
+            texts.add_text(rng.integers(1000, 30522, size=max(n - 2, 0)))
+    return texts.finalize()
+
+
 def adversarial_objects(n_pts: int = 1024, seed: int = 7) -> torch.Tensor:
     """(6, n_pts, 3) xyz clouds that stress the bit-exactness rules of SURVEY.md App. B:
     0 heavy duplicates (FPS ties), 1 many points inside |p|^2 <= 1e-3 (FPS skip rule),
