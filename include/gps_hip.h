@@ -778,6 +778,50 @@ GPS_API int gps_text_batch(int n_texts, long long n_tok, const int32_t *tok, con
                            int64_t *txt_masks, int64_t *masked_lm_labels, int64_t *scene_txt_ids,
                            int64_t *scene_txt_masks, uint8_t *obj_sem_masks, gps_stream_t stream);
 
+/* ---- which objects of a scan enter the batch: background filter, crop, random fill ----------------------
+ * Replaces, per batch and in ONE launch (no atomics, no workspace, no scratch, no host sync; capturable), the object
+ * selection of ScanBase._getitem_pretrain (data/datasets/base.py:231-246), _getitem_obj_pretrain (base.py:275-289),
+ * _getitem_refer (base.py:368-450) and _getitem_finalrefer (base.py:877-957) for `pc_type: 'gt'`, and the is_multiple /
+ * is_hard look-ups of base.py:485-488 / :992-994 over the label counts of data/datasets/scannet.py:70-76.  The row table
+ * it writes is the `row_obj` of gps_obj_processing_post / _aug and gps_refer_targets.
+ *   labels (n_objects) int32 per resident object; scan_range (B, 2) int32 [first, last) global ids of each row's scan,
+ *   clamped to [0, n_objects]; tgt_obj (B) int32 GLOBAL id of the referred object (refer mode; NULL in pre-train mode);
+ *   keep: u8 table, label l is kept for row b iff keep[b * keep_stride + l] != 0 -- keep_stride 0: one (n_labels) table
+ *   for all rows, keep_stride n_labels: (B, n_labels), one per row (filter_lang); label_map (n_labels) int32 or NULL =
+ *   identity (the reference's id_to_scannetid); M = the number of objects a row may hold, M <= O.
+ *   Outputs, every element written: row_obj (B, O) int32 global ids, -1 past the row's length; tgt_slot, n_sel, n_rem
+ *   (B) int32; is_multiple, is_hard (B) u8.
+ * Per row b: positions p = 0 .. last - first - 1 with l_p = labels[first + p]; valid_p = 0 <= l_p < n_labels;
+ *   kept_p = valid_p && keep[..][l_p].  t = tgt_obj[b] - first.
+ *   sel = the kept positions ascending; refer mode: t appended LAST when it is not kept.  n = len(sel).
+ *   n <= M: the row is sel, tgt_slot = index of t in it (-1 in pre-train mode), n_rem = 0.
+ *   n > M, refer: t first; then the other entries of sel with l_p == l_t (raw labels) in sel order, the row cut at M
+ *     entries; if it is shorter than M, remained = the entries of sel with l_p != l_t in sel order and the row is
+ *     completed with remained[order[0]], remained[order[1]], ...; tgt_slot = 0.
+ *   n > M, pre-train: remained = sel, the row is remained[order[0 .. M - 1]].
+ *   n_sel = the row's length; n_rem = len(remained) when the fill ran, else 0.
+ *   is_multiple = more than 1 valid position of the scan (background included) has map(l_p) == map(l_t); is_hard = more
+ *   than 2 have l_p == l_t; both 0 in pre-train mode and when l_t is not valid.
+ *   A refer row whose t is outside [0, last - first), and any row of more than GPS_OBJ_SELECT_MAX_SCAN positions, comes
+ *   out EMPTY: row -1, n_sel = n_rem = 0, tgt_slot = -1, flags 0.  No id read from device memory becomes an address
+ *   unchecked.
+ * order, replay form: (B, R) int32, R >= M, row b = what random.shuffle made of list(range(n_rem)); only the first
+ *   M - (entries already placed) are read; an entry outside [0, n_rem) writes -1.
+ * order == NULL, the device law: S = seed + (seed_dev ? *seed_dev : 0); remained is taken in ascending order of the
+ *   64-bit key (uint64(rng_u32(S + 3, b * 2^20 + r)) << 32) | r, r = the index into remained (csrc/gps_dropout.h; S + 3
+ *   follows the three streams of gps_text_batch, so one seed word serves both launches).
+ * GPS_ERR_INVALID_ARGUMENT: a negative size, M < 1, M > O, mode not 0 / 1, keep_stride not 0 / n_labels, order given
+ *   with R < M, a NULL mandatory pointer (B > 0).  GPS_ERR_UNSUPPORTED: refer mode with M < 2 (the reference itself
+ *   overshoots there), O > GPS_REFER_MAX_OBJ.  B == 0: GPS_OK, nothing launched. */
+#define GPS_OBJ_SELECT_MAX_SCAN 1024
+#define GPS_OBJ_SELECT_REFER 0
+#define GPS_OBJ_SELECT_PRETRAIN 1
+GPS_API int gps_obj_select(int B, int O, int M, int mode, int n_objects, int n_labels, const int32_t *labels,
+                           const int32_t *scan_range, const int32_t *tgt_obj, const uint8_t *keep, int keep_stride,
+                           const int32_t *label_map, const int32_t *order, int R, uint64_t seed,
+                           const uint64_t *seed_dev, int32_t *row_obj, int32_t *tgt_slot, int32_t *n_sel,
+                           int32_t *n_rem, uint8_t *is_multiple, uint8_t *is_hard, gps_stream_t stream);
+
 /* ---- accuracy counters of the pre-train, ReferIt3D and object-class evaluators -------------------------
  * Replaces the arg-max / compare / sum / `.item()` chains of PretrainEval.batch_metrics (evaluator/pretrain_eval.py:21-67),
  * ReferIt3DEval.batch_metrics (evaluator/referit3d_eval.py:14-83) and PretrainObjEval.batch_metrics

@@ -29,6 +29,7 @@ SOURCES = [
     ("gps_refer.hip", ["-ffp-contract=off"]),
     ("gps_metrics.hip", ["-ffp-contract=off"]),
     ("gps_text.hip", []),
+    ("gps_obj_select.hip", []),
     ("gps_reduce.hip", []),
     ("gps_embedding.hip", []),
     ("gps_bert_embed.hip", []),

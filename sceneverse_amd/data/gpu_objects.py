@@ -9,6 +9,8 @@ Reference (what this replaces on the data-loader workers):
     dataset wrapper padding        data/datasets/dataset_wrapper.py:62-70  pad to max_obj_len, obj_masks
     ScanBase._getitem_refer        data/datasets/base.py:348-417  `pc_type: 'pred'`: predicted proposals (loaded at
                                                                   :115-141), labels / flags / target id by box IoU
+    object selection, 'gt'         data/datasets/base.py:231-246, :275-289, :368-450, :877-957  background filter, target-
+                                                                  first crop, random fill; :485-488 is_multiple / is_hard
 
 MI355X form: every scan is uploaded ONCE in its raw on-disk precision (xyz f32 + rgb u8, packed as
 16-byte records, instead of the loader's 48 B/point float64 rows), points regrouped so that each kept instance is
@@ -164,6 +166,144 @@ def batch_rows(packed: PackedScans, scan_ids: Sequence[str], max_obj_len: int,
     return torch.from_numpy(rows)
 
 
+def scan_ranges(packed: PackedScans, scan_ids) -> torch.Tensor:
+    """(B, 2) int32 [first, last) global ids of the scans' annotated objects, on the scans' device: what `select_rows`
+    and `refer_targets` read.  A tensor of that form is passed through (after a shape / dtype / device check), so a
+    loader builds the table once per batch, or once per epoch, outside any captured region."""
+    dev = packed.xyz.device
+    if torch.is_tensor(scan_ids):
+        if scan_ids.dim() != 2 or scan_ids.shape[1] != 2 or scan_ids.dtype != torch.int32 or scan_ids.device != dev:
+            raise ValueError("scan_ranges: a range table must be (B, 2) int32 on the scans' device")
+        return scan_ids.contiguous()
+    ranges = np.asarray([[r.start, r.stop] for r in (packed.scan_objects(s) for s in scan_ids)],
+                        dtype=np.int32).reshape(len(scan_ids), 2)
+    return torch.from_numpy(ranges).to(dev)
+
+
+# ---- which objects enter the batch: filter, crop, random fill ------------------------------------------------
+OBJ_SELECT_MAX_SCAN = 1024                       # GPS_OBJ_SELECT_MAX_SCAN of include/gps_hip.h
+_SELECT_MODES = {"refer": 0, "pretrain": 1}      # GPS_OBJ_SELECT_REFER / _PRETRAIN
+_SELECT_OUT = (("row_obj", torch.int32), ("tgt_slot", torch.int32), ("n_sel", torch.int32), ("n_rem", torch.int32),
+               ("is_multiple", torch.bool), ("is_hard", torch.bool))
+BACKGROUND = ("wall", "floor", "ceiling")
+
+
+def keep_table(int2cat: Sequence[str], drop: Sequence[str] = BACKGROUND, only: Optional[Sequence[str]] = None) -> torch.Tensor:
+    """(n_labels,) bool: label l is kept iff int2cat[l] is not in `drop` (the loader's wall / floor / ceiling filter,
+    base.py:232-233, :380-381) and, with `only`, is one of those names (`only=CLASS_LABELS_200`: the filter of
+    _getitem_obj_pretrain, base.py:276-277).  For `filter_lang` build a (B, n_labels) table: row b keeps label l iff
+    this table does and `int2cat[l] in sentence_b` (base.py:371-373)."""
+    drop = set(drop)
+    only = None if only is None else set(only)
+    return torch.tensor([(c not in drop) and (only is None or c in only) for c in int2cat], dtype=torch.bool)
+
+
+def select_rows(packed: PackedScans, scan_ids, max_keep: int, O: Optional[int] = None, tgt_obj=None, mode: str = "refer",
+                keep: Optional[torch.Tensor] = None, label_map: Optional[torch.Tensor] = None,
+                order: Optional[torch.Tensor] = None, seed: int = 0, seed_dev: Optional[torch.Tensor] = None,
+                out: Optional[dict] = None) -> dict:
+    """The loader's object selection for `pc_type: 'gt'` (base.py:231-246, :275-289, :368-450, :877-957) for a whole
+    batch in one launch and without a host sync: drop the background (the referred object stays), and where more than
+    `max_keep` objects remain put the target first, then its class, then a random choice of the rest -- redrawn every
+    call.  `batch_rows` only copies ranges and raises on such a scan; the rule is stated in include/gps_hip.h.
+
+    -> dict: row_obj (B, O) int32 global object ids, -1 = padding -- the table `obj_processing_post`, `obj_processing_aug`
+    and `refer_targets(..., "gt")` take; tgt_slot (B) int32, the target's slot (the loader's tgt_object_id; -1 in
+    'pretrain' mode); n_sel (B) int32 objects in the row; n_rem (B) int32, how many objects the random fill chose from
+    (0 = no fill); is_multiple, is_hard (B) bool (base.py:485-488; both False in 'pretrain' mode).
+
+    scan_ids: the rows' scans, or their `scan_ranges` table.  max_keep: objects a row may hold -- the loader's
+    `max_obj_len`, which ScanNetSpatialRefer sets to the config's value - 1 (scannet.py:50).  O: slots per row,
+    default max_keep + 1 in 'refer' mode (refer_targets' flag vectors need one spare slot) and max_keep in 'pretrain'.
+    tgt_obj: per row the position of the referred object among its scan's annotated objects, as in `refer_targets`.
+    keep: `keep_table(...)`, (n_labels,) or per row (B, n_labels), bool / uint8.  label_map: (n_labels,) the reference's
+    id_to_scannetid for is_multiple (ScanNetSpatialRefer); None = identity, the _getitem_finalrefer form.
+    order: (B, R >= max_keep) int32, per row what `random.shuffle` made of `list(range(n_rem))` -- a replay of the
+    reference's draw; None = drawn on the device from seed + *seed_dev by the law of include/gps_hip.h (seed_dev: one
+    int64 word on the device, advanced there between graph replays; the stream is seed + 3, so `text_batch` can share
+    the word).  out: optional dict of preallocated contiguous tensors under the names above (int32; the flags bool or
+    uint8), written IN PLACE.
+    A scan of more than OBJ_SELECT_MAX_SCAN objects, max_keep > O and a target given on the host outside its scan are
+    refused here (ValueError); in a device table such a row comes out empty (n_sel 0, tgt_slot -1)."""
+    if packed.xyz is None:
+        raise RuntimeError("PackedScans.finalize() has not been called")
+    if mode not in _SELECT_MODES:
+        raise ValueError(f"select_rows: mode {mode!r} is neither 'refer' nor 'pretrain'")
+    refer = mode == "refer"
+    M = int(max_keep)
+    if O is None:
+        O = M + 1 if refer else M
+    O = int(O)
+    if M < 1 or M > O:
+        raise ValueError(f"select_rows: max_keep {M} must lie in [1, O = {O}]")
+    if refer and M < 2:
+        raise ValueError("select_rows: 'refer' mode needs max_keep >= 2")
+    if O > REFER_MAX_OBJ:
+        raise ValueError(f"select_rows: {O} object slots > {REFER_MAX_OBJ}")
+    if refer and tgt_obj is None:
+        raise ValueError("select_rows: 'refer' mode needs tgt_obj")
+    if keep is None:
+        raise ValueError("select_rows: keep is required (see keep_table)")
+    host_ids = not torch.is_tensor(scan_ids)
+    B = len(scan_ids)
+    if host_ids:
+        sizes = [len(packed.scan_objects(s)) for s in scan_ids]
+        for sid, n in zip(scan_ids, sizes):
+            if n > OBJ_SELECT_MAX_SCAN:
+                raise ValueError(f"select_rows: scan {sid} has {n} objects > {OBJ_SELECT_MAX_SCAN}")
+    tgt = None
+    if refer:
+        tgt = torch.as_tensor(tgt_obj).reshape(-1)
+        if tgt.numel() == 0:                     # an empty list has no integer dtype of its own
+            tgt = tgt.to(torch.int32)
+        if tgt.numel() != B or tgt.dtype.is_floating_point or tgt.dtype == torch.bool:
+            raise ValueError(f"select_rows: tgt_obj must hold {B} integer positions")
+        if host_ids and tgt.device.type == "cpu" and any(not 0 <= int(t) < n for t, n in zip(tgt.tolist(), sizes)):
+            raise ValueError("select_rows: a target position outside its scan")
+    dev = packed.xyz.device
+    if dev.type != "cuda":
+        raise RuntimeError("select_rows runs on libgps_hip.so: scenes must live on a GPU (no CPU path)")
+    ranges = scan_ranges(packed, scan_ids)
+    if refer:
+        tgt = tgt.to(device=dev, dtype=torch.int32) + ranges[:, 0]
+    if keep.dtype not in (torch.bool, torch.uint8) or keep.dim() not in (1, 2) or (keep.dim() == 2 and keep.shape[0] != B):
+        raise ValueError("select_rows: keep must be (n_labels,) or (B, n_labels) bool / uint8")
+    keep = keep.to(dev).contiguous()
+    n_labels = int(keep.shape[-1])
+    if label_map is not None:
+        if label_map.shape != (n_labels,) or label_map.dtype.is_floating_point:
+            raise ValueError(f"select_rows: label_map must hold {n_labels} integers")
+        label_map = label_map.to(device=dev, dtype=torch.int32).contiguous()
+    R = 0
+    if order is not None:
+        if order.dim() != 2 or order.shape[0] != B or order.shape[1] < M or order.dtype.is_floating_point:
+            raise ValueError(f"select_rows: order must be (B, R >= {M}) integers")
+        order = order.to(device=dev, dtype=torch.int32).contiguous()
+        R = int(order.shape[1])
+    if seed_dev is not None and (seed_dev.device != dev or seed_dev.dtype != torch.int64 or seed_dev.numel() != 1):
+        raise ValueError("select_rows: seed_dev must be one int64 word on the scans' GPU")
+    shapes = {name: ((B, O) if name == "row_obj" else (B,)) for name, _ in _SELECT_OUT}
+    if out is not None:
+        res = {}
+        for name, dt in _SELECT_OUT:
+            t = out.get(name)
+            dtypes = (torch.bool, torch.uint8) if dt == torch.bool else (dt,)
+            if t is None or tuple(t.shape) != shapes[name] or t.dtype not in dtypes or not t.is_contiguous() or t.device != dev:
+                raise ValueError(f"select_rows: out[{name!r}] must be a contiguous {shapes[name]} {dt} tensor on the scans' GPU")
+            res[name] = t
+    else:
+        res = {name: torch.empty(shapes[name], dtype=dt, device=dev) for name, dt in _SELECT_OUT}
+    launch("gps_obj_select", B, O, M, _SELECT_MODES[mode], packed.n_objects, n_labels, packed.labels, ranges, tgt, keep,
+           n_labels if keep.dim() == 2 else 0, label_map, order, R, int(seed) & ((1 << 64) - 1), seed_dev,
+           res["row_obj"], res["tgt_slot"], res["n_sel"], res["n_rem"], res["is_multiple"], res["is_hard"], device=dev,
+           label=f"obj_select(B={B},O={O},M={M})", nbytes=4 * B * (O + 6) + 2 * B + 4 * B * OBJ_SELECT_MAX_SCAN // 4,
+           what="select_rows")     # outputs + ranges and target + a label per position (scans of some 256 objects)
+    for name in ("is_multiple", "is_hard"):
+        if res[name].dtype != torch.bool:
+            res[name] = res[name].bool()
+    return res
+
+
 def obj_processing_post(packed: PackedScans, row_obj: torch.Tensor, num_points: int = 1024,
                         rot: Optional[torch.Tensor] = None, sample_idx: Optional[torch.Tensor] = None,
                         seed: int = 0, need_boxes: bool = False, out: Optional[dict] = None) -> dict:
@@ -267,12 +407,13 @@ def refer_targets(packed: PackedScans, row_obj: torch.Tensor, tgt_obj, scan_ids:
 
     row_obj (B,O) int32: batch_rows(..., proposals=True) for pc_type 'pred', batch_rows(...) for 'gt'.
     tgt_obj: per item the position of the referred object among its scan's annotated objects (`obj_ids.index(
-    tgt_object_instance)`, base.py:398), a sequence or a tensor on any device.  scan_ids: the items' scans.
+    tgt_object_instance)`, base.py:398), a sequence or a tensor on any device.  scan_ids: the items' scans, or their
+    `scan_ranges(packed, scan_ids)` table made ahead of the call (no upload inside a captured region then).
     out: optional dict of preallocated contiguous tensors of those four names, shapes and dtypes, written IN PLACE.
     The reference's flag vectors have n_b + 1 entries, so a scene that fills all O slots cannot be padded there
     (pad_tensors asserts); a row table on the host is checked for that here (ValueError), one on the device is not.
     Integer-stored colours: bit-equal flags; float32-stored colours: the float64 form still (the reference's float32
-    boxes are no parity target).  `is_multiple` / `is_hard` stay dictionary look-ups of the caller."""
+    boxes are no parity target).  `is_multiple` / `is_hard` are dictionary look-ups of the caller, or `select_rows`'."""
     if packed.xyz is None:
         raise RuntimeError("PackedScans.finalize() has not been called")
     if pc_type not in ("pred", "gt"):
@@ -288,9 +429,7 @@ def refer_targets(packed: PackedScans, row_obj: torch.Tensor, tgt_obj, scan_ids:
     if dev.type != "cuda":
         raise RuntimeError("refer_targets runs on libgps_hip.so: scenes must live on a GPU (no CPU path)")
     row_obj = row_obj.to(device=dev, dtype=torch.int32).contiguous()
-    ranges = np.asarray([[r.start, r.stop] for r in (packed.scan_objects(s) for s in scan_ids)],
-                        dtype=np.int32).reshape(B, 2)
-    ranges = torch.from_numpy(ranges).to(dev)
+    ranges = scan_ranges(packed, scan_ids)
     tgt = torch.as_tensor(tgt_obj).reshape(B).to(device=dev, dtype=torch.int32) + ranges[:, 0]
     shapes = {name: (B, w if w is not None else O) for name, w in _REFER_OUT}
     if out is not None:
