@@ -822,6 +822,72 @@ GPS_API int gps_obj_select(int B, int O, int M, int mode, int n_objects, int n_l
                            const uint64_t *seed_dev, int32_t *row_obj, int32_t *tgt_slot, int32_t *n_sel,
                            int32_t *n_rem, uint8_t *is_multiple, uint8_t *is_hard, gps_stream_t stream);
 
+/* ---- which PROPOSALS of a scan enter a `pc_type: 'pred'` ScanRefer row: IoU hits, crop, random fill ----------
+ * Replaces the proposal relabelling of ScanBase._getitem_refer (data/datasets/base.py:353-366), its target lists
+ * (base.py:396-417), its crop (base.py:420-450, with max_obj_len lowered by ScanNetSpatialRefer, data/datasets/
+ * scannet.py:50) and the look-ups of base.py:453-454, :478-488 over the label counts of scannet.py:70-76.
+ *
+ * gps_proposal_labels: once per set of resident scans, ONE launch, one thread per proposal.  boxes (n_objects, 6)
+ *   float64 and labels (n_objects) int32 as in gps_refer_targets; prop_id (n_props) int32 the proposal's global id;
+ *   ann_range (n_props, 2) int32 [first, last) global ids of ITS scan's annotated objects, clamped to [0, n_objects].
+ *   match_labels[prop_id[i]] = labels[j] of the FIRST j in [first, last) with iou(box j, box prop_id[i]) >= 0.25, else
+ *   labels[prop_id[i]] -- the arithmetic of gps_refer_targets (float64, no contraction), so the value is bit-equal to
+ *   the obj_labels entry gps_refer_targets('pred') writes for that proposal.  Entries of match_labels that are no
+ *   proposal are NOT written: the caller fills them with the objects' own labels first.  A prop_id outside
+ *   [0, n_objects) is skipped.  n_props == 0: GPS_OK, nothing launched; a negative size or a NULL pointer:
+ *   GPS_ERR_INVALID_ARGUMENT.
+ *
+ * gps_obj_select_pred: per batch ONE launch (no atomics, no workspace, no scratch, no host sync; capturable).
+ *   boxes, labels as above; match_labels (n_objects) int32 from gps_proposal_labels; scan_range (B, 2) int32 [first,
+ *   last) global ids of the row's ANNOTATED objects and prop_range (B, 2) int32 [pf, pl) of its proposals, both clamped
+ *   to [0, n_objects]; tgt_obj (B) int32 global id of the referred ANNOTATED object; tgt_label (B) int32 or NULL;
+ *   label_map (n_labels) int32 or NULL = identity; M = the number of proposals a row may hold, M <= O <=
+ *   GPS_REFER_MAX_OBJ; order, R, seed, seed_dev as in gps_obj_select.
+ *   Outputs, every element written: row_obj (B, O) int32 global ids, -1 past the row's length; tgt_slot, n_sel, n_rem
+ *   (B) int32; is_multiple, is_hard (B) u8; and, all four or none of them, iou25, iou50 (B, O) int64, tgt_id (B) int64,
+ *   obj_labels (B, O) int64 -- bit-equal to what gps_refer_targets(mode 'pred') writes for that row_obj, from the flags
+ *   and labels the launch already holds (one launch per 'pred' batch, not two).
+ * Per row b: positions p = 0 .. P - 1 (P = pl - pf), g_p = pf + p, m_p = match_labels[g_p].  t = tgt_obj[b];
+ *   l_t = tgt_label[b] when given, else labels[t] (the reference reads cat2int[instance_type], which its 'gt' path asserts
+ *   to be that label).  v_p = iou(box g_p, box t) with the expression of gps_refer_targets; h25_p = v_p >= 0.25,
+ *   h50_p = v_p >= 0.5.
+ *   P <= M: the row is 0 .. P - 1, n_rem = 0.
+ *   P > M: pinned = the positions with h25_p, ASCENDING; k = len(pinned).
+ *     k >= M: the row is the M largest of pinned, ascending.
+ *     otherwise the row is pinned, then the unpinned positions with m_p == l_t ascending, cut at M entries; if it is
+ *     still shorter than M, remained = the unpinned positions with m_p != l_t ascending and the row is completed with
+ *     remained[order[0]], remained[order[1]], ... -- replay form and device law exactly those of gps_obj_select: stream
+ *     S + 3, key (uint64(rng_u32(S + 3, b * 2^20 + r)) << 32) | r, so one seed word serves gps_text_batch and both
+ *     selections.
+ *   tgt_slot = the slot of the LARGEST pinned position in the row, -1 when nothing is pinned.  n_sel = the row's length;
+ *   n_rem = len(remained) when the fill ran, else 0.  tgt_id = tgt_slot, or the number of real slots when it is -1.
+ *   is_multiple = more than 1 ANNOTATED position a of the scan with 0 <= labels[a] < n_labels has map(labels[a]) ==
+ *   map(l_t); is_hard = more than 2 have labels[a] == l_t; both 0 when l_t is outside [0, n_labels).
+ *   EMPTY rows (row -1, n_sel = n_rem = 0, tgt_slot -1, flags 0; iou25 / iou50 0, obj_labels -100, tgt_id 0): t outside
+ *   [first, last); P > GPS_OBJ_SELECT_MAX_SCAN.  P == 0 is a legitimate row of length 0.  No id read from device memory
+ *   becomes an address unchecked.
+ * Two differences from the reference, both on purpose:
+ *   the pinned block.  The reference builds it with list(set(...)) (base.py:427), i.e. in CPython's hash-table order
+ *   ({3, 9} iterates 9, 3); this entry takes ascending order.  Against the reference tgt_object_id_iou25 is equal bit
+ *   for bit (the block is all ones either way), the row behind the block is equal as a sequence, the block is equal as a
+ *   set, the object in tgt_object_id's slot is the same object, the set of objects flagged at 0.5 is the same and
+ *   obj_labels agree per object.
+ *   rows the reference cannot run.  With no proposal at IoU >= 0.25 and P > M the reference keeps its stale full list
+ *   and fails its own assertion (base.py:423-450); with k > M it overshoots.  Both are defined above.
+ * GPS_ERR_INVALID_ARGUMENT: a negative size, M < 1, M > O, order given with R < M, the four target outputs given in
+ *   part, a NULL mandatory pointer (B > 0).  GPS_ERR_UNSUPPORTED: M < 2, O > GPS_REFER_MAX_OBJ.  B == 0: GPS_OK, nothing
+ *   launched. */
+GPS_API int gps_proposal_labels(int n_props, int n_objects, const double *boxes, const int32_t *labels,
+                                const int32_t *prop_id, const int32_t *ann_range, int32_t *match_labels,
+                                gps_stream_t stream);
+GPS_API int gps_obj_select_pred(int B, int O, int M, int n_objects, int n_labels, const double *boxes,
+                                const int32_t *labels, const int32_t *match_labels, const int32_t *scan_range,
+                                const int32_t *prop_range, const int32_t *tgt_obj, const int32_t *tgt_label,
+                                const int32_t *label_map, const int32_t *order, int R, uint64_t seed,
+                                const uint64_t *seed_dev, int32_t *row_obj, int32_t *tgt_slot, int32_t *n_sel,
+                                int32_t *n_rem, uint8_t *is_multiple, uint8_t *is_hard, int64_t *iou25,
+                                int64_t *iou50, int64_t *tgt_id, int64_t *obj_labels, gps_stream_t stream);
+
 /* ---- accuracy counters of the pre-train, ReferIt3D and object-class evaluators -------------------------
  * Replaces the arg-max / compare / sum / `.item()` chains of PretrainEval.batch_metrics (evaluator/pretrain_eval.py:21-67),
  * ReferIt3DEval.batch_metrics (evaluator/referit3d_eval.py:14-83) and PretrainObjEval.batch_metrics

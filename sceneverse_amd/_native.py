@@ -151,6 +151,8 @@ SIGNATURES = {
     "gps_text_batch": [_i, ctypes.c_longlong, _vp, _vp, _i, _vp, _vp] + [_i] * 9 + [ctypes.c_double, ctypes.c_double,
                        _i, _i, _vp, _vp, _vp, _vp, ctypes.c_ulonglong] + [_vp] * 8,
     "gps_obj_select": [_i] * 6 + [_vp] * 4 + [_i, _vp, _vp, _i, ctypes.c_ulonglong] + [_vp] * 8,
+    "gps_proposal_labels": [_i, _i] + [_vp] * 6,
+    "gps_obj_select_pred": [_i] * 5 + [_vp] * 9 + [_i, ctypes.c_ulonglong] + [_vp] * 12,
     "gps_cls_hits": [ctypes.POINTER(ClsHitsProblem), _i, _vp],
     "gps_metrics_fold": [_i, ctypes.POINTER(MetricTerm), ctypes.c_double, _i, _vp, _vp, _vp, _vp],
     "gps_embedding_grad_scratch_ints": [_i, _i, _i],

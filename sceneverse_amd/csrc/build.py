@@ -30,6 +30,7 @@ SOURCES = [
     ("gps_metrics.hip", ["-ffp-contract=off"]),
     ("gps_text.hip", []),
     ("gps_obj_select.hip", []),
+    ("gps_obj_select_pred.hip", ["-ffp-contract=off"]),
     ("gps_reduce.hip", []),
     ("gps_embedding.hip", []),
     ("gps_bert_embed.hip", []),

@@ -12,6 +12,8 @@
 // gps_obj_select   ONE launch, no atomics, no workspace, no scratch, no host sync; every element of every output is
 //   written.  Grid: one workgroup of kBlock = GPS_OBJ_SELECT_MAX_SCAN threads (16 waves) per row, thread p = position p
 //   of the row's scan.  The rule is stated in include/gps_hip.h; tests/rows_cases.py restates it in numpy.
+//   The ballot compaction and the rank loop described below are csrc/gps_rows_dev.h's (seg_ballot / seg_sums, fill_key /
+//   key_ranks), shared with the selection of predicted proposals (gps_obj_select_pred.hip); wave w is its segment w.
 //   * One pass of five ballots per wave: kept, class-mate of the target, remained, same mapped label, same raw label.
 //     A lane's rank inside its wave is the popcount of the ballot below it; lane 0 of each wave leaves the wave's five
 //     counts in LDS, and after ONE barrier every thread adds up the waves before its own (16 words, the same address in
@@ -35,11 +37,13 @@
 #include "gps_dev.h"
 #include "gps_dropout.h"
 #include "gps_hip.h"
+#include "gps_rows_dev.h"
 
 namespace gps_obj_select_ns {
 
 constexpr int kBlock = GPS_OBJ_SELECT_MAX_SCAN;  // 1024: one thread per scan position
 constexpr int kWaves = kBlock / 64;
+static_assert(kWaves == gps_rows::kSegs, "wave w holds segment w of csrc/gps_rows_dev.h");
 constexpr int kMaxSlots = GPS_REFER_MAX_OBJ;    // O <= 512
 enum Count { kKept = 0, kCls = 1, kRem = 2, kMulti = 3, kHard = 4, kCounts = 5 };
 
@@ -109,30 +113,22 @@ __global__ __launch_bounds__(kBlock) void obj_select_kernel(const Params p) {
   const bool multi = refer && lt_valid && valid && mapped == map_t;
   const bool hard = refer && lt_valid && valid && l == l_t;
 
-  const unsigned long long below = (1ull << lane) - 1ull;
-  const unsigned long long m_kept = __ballot(kept), m_cls = __ballot(is_cls), m_rem = __ballot(is_rem);
-  const unsigned long long m_multi = __ballot(multi), m_hard = __ballot(hard);
-  if (lane == 0) {
-    s_cnt[kKept][wave] = __popcll(m_kept);
-    s_cnt[kCls][wave] = __popcll(m_cls);
-    s_cnt[kRem][wave] = __popcll(m_rem);
-    s_cnt[kMulti][wave] = __popcll(m_multi);
-    s_cnt[kHard][wave] = __popcll(m_hard);
-  }
+  // the ordered compaction of csrc/gps_rows_dev.h: wave w is segment w
+  const int in_kept = gps_rows::seg_ballot(kept, s_cnt[kKept], wave, lane);
+  const int in_cls = gps_rows::seg_ballot(is_cls, s_cnt[kCls], wave, lane);
+  const int in_rem = gps_rows::seg_ballot(is_rem, s_cnt[kRem], wave, lane);
+  gps_rows::seg_ballot(multi, s_cnt[kMulti], wave, lane);
+  gps_rows::seg_ballot(hard, s_cnt[kHard], wave, lane);
   __syncthreads();
-  int before[3] = {0, 0, 0}, total[kCounts] = {0, 0, 0, 0, 0};
-#pragma unroll
-  for (int w = 0; w < kWaves; ++w) {
-#pragma unroll
-    for (int c = 0; c < kCounts; ++c) {
-      const int v = s_cnt[c][w];
-      total[c] += v;
-      if (c < 3 && w < wave) before[c] += v;
-    }
-  }
-  const int rank_kept = before[kKept] + __popcll(m_kept & below);
-  const int rank_cls = before[kCls] + __popcll(m_cls & below);
-  const int rank_rem = before[kRem] + __popcll(m_rem & below);
+  int before[3], total[kCounts];
+  total[kKept] = gps_rows::seg_sums(s_cnt[kKept], wave, before[kKept]);
+  total[kCls] = gps_rows::seg_sums(s_cnt[kCls], wave, before[kCls]);
+  total[kRem] = gps_rows::seg_sums(s_cnt[kRem], wave, before[kRem]);
+  total[kMulti] = gps_rows::seg_total(s_cnt[kMulti]);
+  total[kHard] = gps_rows::seg_total(s_cnt[kHard]);
+  const int rank_kept = before[kKept] + in_kept;
+  const int rank_cls = before[kCls] + in_cls;
+  const int rank_rem = before[kRem] + in_rem;
   const int n_kept = total[kKept], n_cls = total[kCls], n_remained = total[kRem];
 
   // kept_t is known to thread t only; n needs it everywhere: t is kept iff it counts among the kept of its class
@@ -172,22 +168,14 @@ __global__ __launch_bounds__(kBlock) void obj_select_kernel(const Params p) {
       } else {
         // the 64-bit key itself goes to LDS: one 64-bit compare per pair of keys instead of three 32-bit ones.  The key
         // past n_rem that completes the last pair is all ones, above every real key (their low word is below 1024)
-        const unsigned long long key = tid < n_remained
-            ? ((unsigned long long)gps_dropout::rng_u32(S + 3ull, ((unsigned long long)b << 20) + (unsigned long long)tid) << 32) |
-                  (unsigned long long)tid
-            : ~0ull;
+        const unsigned long long key[1] = {tid < n_remained ? gps_rows::fill_key(S, b, tid) : gps_rows::kPadKey};
         const int n_pairs = (n_remained + 1) >> 1;           // <= kBlock / 2
-        if (tid < 2 * n_pairs) s_key[tid] = key;
+        if (tid < 2 * n_pairs) s_key[tid] = key[0];
         __syncthreads();
         if (tid < n_remained) {
-          int rank = 0;
-#pragma unroll 4
-          for (int q = 0; q < n_pairs; ++q) {
-            const ulonglong2 k2 = reinterpret_cast<const ulonglong2 *>(s_key)[q];    // the same 16 bytes in every lane
-            rank += k2.x < key ? 1 : 0;
-            rank += k2.y < key ? 1 : 0;
-          }
-          if (rank < n_free) s_row[row_len + rank] = first + s_rem[tid];
+          int rank[1];
+          gps_rows::key_ranks(s_key, n_pairs, key, rank);
+          if (rank[0] < n_free) s_row[row_len + rank[0]] = first + s_rem[tid];
         }
       }
       row_len = M;

@@ -27,6 +27,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gps_box_dev.h"
 #include "gps_hip.h"
 
 namespace gps_refer {
@@ -129,28 +130,8 @@ __global__ __launch_bounds__(kBlock) void boxes_finish_kernel(int n_objects, con
 }
 
 // ---- targets ----------------------------------------------------------------------------------------------------------
-struct Box {
-  double lo[3], hi[3], vol;
-  // construct_bbox_corners + get_box3d_min_max: the corners are c + s/2 and c + (-(s/2)); s >= 0
-  __device__ __forceinline__ void load(const double *__restrict__ b) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const double h = b[3 + c] / 2.0;
-      lo[c] = b[c] + (-h);
-      hi[c] = b[c] + h;
-    }
-    vol = ((hi[0] - lo[0]) * (hi[1] - lo[1])) * (hi[2] - lo[2]);
-  }
-};
-
-// box3d_iou, data/data_utils.py:221-232, in its own order of operations (this file is compiled without contraction)
-__device__ __forceinline__ double iou(const Box &a, const Box &b) {
-  const double dx = fmin(a.hi[0], b.hi[0]) - fmax(a.lo[0], b.lo[0]);
-  const double dy = fmin(a.hi[1], b.hi[1]) - fmax(a.lo[1], b.lo[1]);
-  const double dz = fmin(a.hi[2], b.hi[2]) - fmax(a.lo[2], b.lo[2]);
-  const double inter = (fmax(dx, 0.0) * fmax(dy, 0.0)) * fmax(dz, 0.0);
-  return inter / (((a.vol + b.vol) - inter) + 1e-8);
-}
+using gps_box::Box;                             // the box and box3d_iou: csrc/gps_box_dev.h, shared with the
+using gps_box::iou;                             // proposal selection (gps_obj_select_pred.hip)
 
 constexpr int kMaxSlots = GPS_REFER_MAX_OBJ;    // 512: eight waves
 

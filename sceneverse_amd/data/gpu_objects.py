@@ -49,7 +49,7 @@ class PackedScans:
         self._inst_ids: Dict[str, list] = {}
         self._labels: List[int] = []
         self.xyz = self.rgb = self.obj_offsets = None
-        self.labels = self.boxes = None
+        self.labels = self.boxes = self.match_labels = None
         self.sizes_host: Optional[np.ndarray] = None
 
     def add_scan(self, scan_id: str, points: np.ndarray, colors: np.ndarray, instance_labels: np.ndarray,
@@ -132,6 +132,7 @@ class PackedScans:
         self._xyz, self._rgb = [], []
         if self.device.type == "cuda":             # the boxes are a device product: no CPU path
             self.boxes = obj_boxes(self)
+            self.match_labels = proposal_labels(self)
         return self
 
     def scan_objects(self, scan_id: str) -> range:
@@ -161,21 +162,25 @@ def batch_rows(packed: PackedScans, scan_ids: Sequence[str], max_obj_len: int,
         if obj_select is not None:
             objs = [objs[i] for i in obj_select[b]]
         if len(objs) > max_obj_len:
-            raise ValueError(f"scan {sid}: {len(objs)} objects > max_obj_len {max_obj_len}")
+            hint = '; select_rows(pc_type="pred") crops such a scan' if proposals else ""
+            raise ValueError(f"scan {sid}: {len(objs)} objects > max_obj_len {max_obj_len}{hint}")
         rows[b, :len(objs)] = objs
     return torch.from_numpy(rows)
 
 
-def scan_ranges(packed: PackedScans, scan_ids) -> torch.Tensor:
+def scan_ranges(packed: PackedScans, scan_ids, proposals: bool = False) -> torch.Tensor:
     """(B, 2) int32 [first, last) global ids of the scans' annotated objects, on the scans' device: what `select_rows`
     and `refer_targets` read.  A tensor of that form is passed through (after a shape / dtype / device check), so a
-    loader builds the table once per batch, or once per epoch, outside any captured region."""
+    loader builds the table once per batch, or once per epoch, outside any captured region.
+    proposals=True: the ranges of the scans' proposals (`add_proposals`; KeyError for a scan without them), the second
+    table `select_rows(pc_type="pred")` reads."""
     dev = packed.xyz.device
     if torch.is_tensor(scan_ids):
         if scan_ids.dim() != 2 or scan_ids.shape[1] != 2 or scan_ids.dtype != torch.int32 or scan_ids.device != dev:
             raise ValueError("scan_ranges: a range table must be (B, 2) int32 on the scans' device")
         return scan_ids.contiguous()
-    ranges = np.asarray([[r.start, r.stop] for r in (packed.scan_objects(s) for s in scan_ids)],
+    of = packed.scan_proposals if proposals else packed.scan_objects
+    ranges = np.asarray([[r.start, r.stop] for r in (of(s) for s in scan_ids)],
                         dtype=np.int32).reshape(len(scan_ids), 2)
     return torch.from_numpy(ranges).to(dev)
 
@@ -201,7 +206,7 @@ def keep_table(int2cat: Sequence[str], drop: Sequence[str] = BACKGROUND, only: O
 def select_rows(packed: PackedScans, scan_ids, max_keep: int, O: Optional[int] = None, tgt_obj=None, mode: str = "refer",
                 keep: Optional[torch.Tensor] = None, label_map: Optional[torch.Tensor] = None,
                 order: Optional[torch.Tensor] = None, seed: int = 0, seed_dev: Optional[torch.Tensor] = None,
-                out: Optional[dict] = None) -> dict:
+                out: Optional[dict] = None, pc_type: str = "gt", tgt_label=None, targets: bool = False) -> dict:
     """The loader's object selection for `pc_type: 'gt'` (base.py:231-246, :275-289, :368-450, :877-957) for a whole
     batch in one launch and without a host sync: drop the background (the referred object stays), and where more than
     `max_keep` objects remain put the target first, then its class, then a random choice of the rest -- redrawn every
@@ -224,12 +229,34 @@ def select_rows(packed: PackedScans, scan_ids, max_keep: int, O: Optional[int] =
     the word).  out: optional dict of preallocated contiguous tensors under the names above (int32; the flags bool or
     uint8), written IN PLACE.
     A scan of more than OBJ_SELECT_MAX_SCAN objects, max_keep > O and a target given on the host outside its scan are
-    refused here (ValueError); in a device table such a row comes out empty (n_sel 0, tgt_slot -1)."""
+    refused here (ValueError); in a device table such a row comes out empty (n_sel 0, tgt_slot -1).
+
+    pc_type="pred": the rows are filled from the scans' PROPOSALS (`add_proposals`).
+    'refer' mode is the crop of base.py:420-450 in one launch of gps_obj_select_pred (rule and its two differences from
+    the reference: include/gps_hip.h): every proposal that overlaps the referred annotated object by IoU >= 0.25 first,
+    in ascending order, then the proposals of the target's class by `packed.match_labels`, then the random fill.  `keep`
+    is not read (the reference filters nothing there; given, only its width bounds the labels that count);
+    tgt_label: (B,) the reference's `cat2int[instance_type]` where it differs from the target's own label, None = that
+    label.  scan_ids: the scans, or the pair (scan_ranges(packed, ids), scan_ranges(packed, ids, proposals=True)) of
+    device tables.  tgt_slot is the slot of the LAST overlapping proposal, -1 when there is none.  targets=True: the
+    result also carries tgt_object_id_iou25 / _iou50 (B, O) int64, tgt_object_id (B, 1) int64 and obj_labels (B, O)
+    int64 in `refer_targets`' layouts, bit-equal to `refer_targets(row_obj, ..., "pred")` -- a 'pred' batch is one
+    launch; `out=` accepts them too.
+    'pretrain' mode is _getitem_pretrain on inst_labels_pred (base.py:227-246): the 'gt' selection over the proposals'
+    ranges with their raw labels (scan_ids: the scans or their proposals' range table)."""
     if packed.xyz is None:
         raise RuntimeError("PackedScans.finalize() has not been called")
     if mode not in _SELECT_MODES:
         raise ValueError(f"select_rows: mode {mode!r} is neither 'refer' nor 'pretrain'")
+    if pc_type not in ("gt", "pred"):
+        raise ValueError(f"select_rows: pc_type {pc_type!r} is neither 'gt' nor 'pred'")
     refer = mode == "refer"
+    pred = pc_type == "pred"
+    if (tgt_label is not None or targets) and not (pred and refer):
+        raise ValueError("select_rows: tgt_label and targets belong to pc_type='pred' in 'refer' mode")
+    if pred and refer:
+        return _select_rows_pred(packed, scan_ids, int(max_keep), O, tgt_obj, keep, label_map, order, seed, seed_dev, out,
+                                 tgt_label, targets)
     M = int(max_keep)
     if O is None:
         O = M + 1 if refer else M
@@ -247,7 +274,7 @@ def select_rows(packed: PackedScans, scan_ids, max_keep: int, O: Optional[int] =
     host_ids = not torch.is_tensor(scan_ids)
     B = len(scan_ids)
     if host_ids:
-        sizes = [len(packed.scan_objects(s)) for s in scan_ids]
+        sizes = [len(_scan_proposals(packed, s) if pred else packed.scan_objects(s)) for s in scan_ids]
         for sid, n in zip(scan_ids, sizes):
             if n > OBJ_SELECT_MAX_SCAN:
                 raise ValueError(f"select_rows: scan {sid} has {n} objects > {OBJ_SELECT_MAX_SCAN}")
@@ -263,7 +290,7 @@ def select_rows(packed: PackedScans, scan_ids, max_keep: int, O: Optional[int] =
     dev = packed.xyz.device
     if dev.type != "cuda":
         raise RuntimeError("select_rows runs on libgps_hip.so: scenes must live on a GPU (no CPU path)")
-    ranges = scan_ranges(packed, scan_ids)
+    ranges = scan_ranges(packed, scan_ids, proposals=pred)
     if refer:
         tgt = tgt.to(device=dev, dtype=torch.int32) + ranges[:, 0]
     if keep.dtype not in (torch.bool, torch.uint8) or keep.dim() not in (1, 2) or (keep.dim() == 2 and keep.shape[0] != B):
@@ -298,6 +325,99 @@ def select_rows(packed: PackedScans, scan_ids, max_keep: int, O: Optional[int] =
            res["row_obj"], res["tgt_slot"], res["n_sel"], res["n_rem"], res["is_multiple"], res["is_hard"], device=dev,
            label=f"obj_select(B={B},O={O},M={M})", nbytes=4 * B * (O + 6) + 2 * B + 4 * B * OBJ_SELECT_MAX_SCAN // 4,
            what="select_rows")     # outputs + ranges and target + a label per position (scans of some 256 objects)
+    for name in ("is_multiple", "is_hard"):
+        if res[name].dtype != torch.bool:
+            res[name] = res[name].bool()
+    return res
+
+
+def _scan_proposals(packed: PackedScans, scan_id) -> range:
+    try:
+        return packed.scan_proposals(scan_id)
+    except KeyError:
+        raise ValueError(f"select_rows: scan {scan_id!r} has no proposals (add_proposals)") from None
+
+
+def _select_rows_pred(packed, scan_ids, M, O, tgt_obj, keep, label_map, order, seed, seed_dev, out, tgt_label, targets):
+    """`select_rows(pc_type="pred")` in 'refer' mode: one launch of gps_obj_select_pred."""
+    O = M + 1 if O is None else int(O)
+    if M < 1 or M > O:
+        raise ValueError(f"select_rows: max_keep {M} must lie in [1, O = {O}]")
+    if M < 2:
+        raise ValueError("select_rows: 'refer' mode needs max_keep >= 2")
+    if O > REFER_MAX_OBJ:
+        raise ValueError(f"select_rows: {O} object slots > {REFER_MAX_OBJ}")
+    if tgt_obj is None:
+        raise ValueError("select_rows: 'refer' mode needs tgt_obj")
+    host_ids = not (isinstance(scan_ids, (tuple, list)) and len(scan_ids) == 2 and all(torch.is_tensor(t) for t in scan_ids))
+    if host_ids and torch.is_tensor(scan_ids):
+        raise ValueError("select_rows: pc_type='pred' takes scan ids or the pair (scan_ranges(..), scan_ranges(.., proposals=True))")
+    B = len(scan_ids) if host_ids else int(scan_ids[0].shape[0])
+    if host_ids:
+        sizes = [len(packed.scan_objects(s)) for s in scan_ids]
+        for sid in scan_ids:
+            n = len(_scan_proposals(packed, sid))
+            if n > OBJ_SELECT_MAX_SCAN:
+                raise ValueError(f"select_rows: scan {sid} has {n} proposals > {OBJ_SELECT_MAX_SCAN}")
+    tgt = torch.as_tensor(tgt_obj).reshape(-1)
+    if tgt.numel() == 0:
+        tgt = tgt.to(torch.int32)
+    if tgt.numel() != B or tgt.dtype.is_floating_point or tgt.dtype == torch.bool:
+        raise ValueError(f"select_rows: tgt_obj must hold {B} integer positions")
+    if host_ids and tgt.device.type == "cpu" and any(not 0 <= int(t) < n for t, n in zip(tgt.tolist(), sizes)):
+        raise ValueError("select_rows: a target position outside its scan")
+    if tgt_label is not None:
+        tgt_label = torch.as_tensor(tgt_label).reshape(-1)
+        if tgt_label.numel() != B or tgt_label.dtype.is_floating_point or tgt_label.dtype == torch.bool:
+            raise ValueError(f"select_rows: tgt_label must hold {B} integer labels")
+    if order is not None and (order.dim() != 2 or order.shape[0] != B or order.shape[1] < M or order.dtype.is_floating_point):
+        raise ValueError(f"select_rows: order must be (B, R >= {M}) integers")
+    dev = packed.xyz.device
+    if dev.type != "cuda":
+        raise RuntimeError("select_rows runs on libgps_hip.so: scenes must live on a GPU (no CPU path)")
+    if host_ids:
+        ranges, props = scan_ranges(packed, scan_ids), scan_ranges(packed, scan_ids, proposals=True)
+    else:
+        ranges, props = scan_ranges(packed, scan_ids[0]), scan_ranges(packed, scan_ids[1])
+        if props.shape[0] != B:
+            raise ValueError("select_rows: the two range tables must have one row per batch row")
+    tgt = tgt.to(device=dev, dtype=torch.int32) + ranges[:, 0]
+    if tgt_label is not None:
+        tgt_label = tgt_label.to(device=dev, dtype=torch.int32).contiguous()
+    n_labels = (1 << 31) - 1                     # without a table every non-negative label counts
+    if keep is not None:
+        n_labels = int(keep.shape[-1])
+    if label_map is not None:
+        if label_map.dim() != 1 or label_map.dtype.is_floating_point or (keep is not None and label_map.shape[0] != n_labels):
+            raise ValueError("select_rows: label_map must hold n_labels integers")
+        n_labels = int(label_map.shape[0])
+        label_map = label_map.to(device=dev, dtype=torch.int32).contiguous()
+    R = 0
+    if order is not None:
+        order = order.to(device=dev, dtype=torch.int32).contiguous()
+        R = int(order.shape[1])
+    if seed_dev is not None and (seed_dev.device != dev or seed_dev.dtype != torch.int64 or seed_dev.numel() != 1):
+        raise ValueError("select_rows: seed_dev must be one int64 word on the scans' GPU")
+    spec = [(name, dt, (B, O) if name == "row_obj" else (B,)) for name, dt in _SELECT_OUT]
+    if targets:
+        spec += [(name, torch.int64, (B, w if w is not None else O)) for name, w in _REFER_OUT]
+    res = {}
+    for name, dt, shape in spec:
+        if out is None:
+            res[name] = torch.empty(shape, dtype=dt, device=dev)
+            continue
+        t = out.get(name)
+        dtypes = (torch.bool, torch.uint8) if dt == torch.bool else (dt,)
+        if t is None or tuple(t.shape) != shape or t.dtype not in dtypes or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"select_rows: out[{name!r}] must be a contiguous {shape} {dt} tensor on the scans' GPU")
+        res[name] = t
+    tout = [res[name] if targets else None for name, _ in _REFER_OUT]
+    launch("gps_obj_select_pred", B, O, M, packed.n_objects, n_labels, packed.boxes, packed.labels, packed.match_labels,
+           ranges, props, tgt, tgt_label, label_map, order, R, int(seed) & ((1 << 64) - 1), seed_dev,
+           res["row_obj"], res["tgt_slot"], res["n_sel"], res["n_rem"], res["is_multiple"], res["is_hard"], *tout,
+           device=dev, label=f"obj_select_pred(B={B},O={O},M={M})",
+           nbytes=4 * B * (O + 8) + 2 * B + (24 * B * O if targets else 0) + 52 * B * 256,
+           what="select_rows")     # outputs + ranges and target + a box and a label per position (scans of some 256 proposals)
     for name in ("is_multiple", "is_hard"):
         if res[name].dtype != torch.bool:
             res[name] = res[name].bool()
@@ -396,6 +516,31 @@ def obj_boxes(packed: PackedScans) -> torch.Tensor:
     launch("gps_obj_boxes", n, int(packed.xyz.shape[0]), int(work.shape[0]), packed.xyz, int(packed.rgb is None), work, ws, boxes,
            device=dev)
     return boxes
+
+
+def proposal_labels(packed: PackedScans) -> torch.Tensor:
+    """(n_objects,) int32: an annotated object's own label; a proposal's label after the relabelling of base.py:353-366
+    -- the label of the first annotated object of its scan whose box overlaps it by IoU >= 0.25, else its own.  It depends
+    on the scan only, so finalize() computes it once (one launch over all proposals) and keeps it as
+    `packed.match_labels`: what `select_rows(pc_type="pred")` reads, bit-equal to `refer_targets(..., "pred")`'s
+    obj_labels for every proposal."""
+    if packed.xyz is None:
+        raise RuntimeError("PackedScans.finalize() has not been called")
+    dev = packed.xyz.device
+    if dev.type != "cuda":
+        raise RuntimeError("proposal_labels runs on libgps_hip.so: scenes must live on a GPU (no CPU path)")
+    match = packed.labels.clone()
+    ids, ann = [], []
+    for sid, props in packed._scan_props.items():
+        objs = packed._scan_objs[sid]
+        ids.extend(props)
+        ann.extend([[objs.start, objs.stop]] * len(props))
+    if ids:
+        prop_id = torch.from_numpy(np.asarray(ids, dtype=np.int32)).to(dev)
+        ann_range = torch.from_numpy(np.asarray(ann, dtype=np.int32).reshape(-1, 2)).to(dev)
+        launch("gps_proposal_labels", len(ids), packed.n_objects, packed.boxes, packed.labels, prop_id, ann_range, match,
+               device=dev)
+    return match
 
 
 def refer_targets(packed: PackedScans, row_obj: torch.Tensor, tgt_obj, scan_ids: Sequence[str], pc_type: str = "pred",
