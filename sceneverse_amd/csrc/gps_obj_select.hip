@@ -68,9 +68,7 @@ __global__ __launch_bounds__(kBlock) void obj_select_kernel(const Params p) {
   const bool refer = p.mode == GPS_OBJ_SELECT_REFER;
 
   int first = p.scan_range[2 * b], last = p.scan_range[2 * b + 1];
-  first = first < 0 ? 0 : first;
-  last = last > p.n_objects ? p.n_objects : last;
-  const int len = last > first ? last - first : 0;
+  const int len = gps_rows::clamp_range(first, last, p.n_objects);
   long long t_ll = -1;
   if (refer) t_ll = (long long)p.tgt_obj[b] - (long long)first;
   const bool tgt_in = t_ll >= 0 && t_ll < (long long)len;

@@ -59,8 +59,7 @@ __global__ __launch_bounds__(kBlock) void proposal_labels_kernel(int n_props, in
   const int g = prop_id[i];
   if (g < 0 || g >= n_objects) return;             // never an address
   int first = ann_range[2 * i], last = ann_range[2 * i + 1];
-  first = first < 0 ? 0 : first;
-  last = last > n_objects ? n_objects : last;
+  gps_rows::clamp_range(first, last, n_objects);
   Box p, q;
   p.load(boxes + (size_t)g * 6);
   int label = labels[g];
@@ -105,11 +104,8 @@ __global__ __launch_bounds__(kBlock) void obj_select_pred_kernel(const Params p)
   int first = p.scan_range[2 * b], last = p.scan_range[2 * b + 1];
   int pf = p.prop_range[2 * b], pl = p.prop_range[2 * b + 1];
   const int tgt = p.tgt_obj[b];
-  first = first < 0 ? 0 : first;
-  last = last > n_objects ? n_objects : last;
-  pf = pf < 0 ? 0 : pf;
-  pl = pl > n_objects ? n_objects : pl;
-  const int P = pl > pf ? pl - pf : 0;
+  gps_rows::clamp_range(first, last, n_objects);
+  const int P = gps_rows::clamp_range(pf, pl, n_objects);
   if (P > gps_rows::kMaxScan || tgt < first || tgt >= last) {     // block-uniform: the empty row
     for (int i = tid; i < O; i += kBlock) {
       p.row_obj[(size_t)b * O + i] = -1;

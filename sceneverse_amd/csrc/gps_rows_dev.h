@@ -1,6 +1,6 @@
-// gps_rows_dev.h -- the two device steps every row selection shares, stated once for gps_obj_select.hip (one thread per
-// position, 16 waves) and gps_obj_select_pred.hip (256 threads, positions strided): the ordered compaction of up to
-// GPS_OBJ_SELECT_MAX_SCAN positions and the seeded fill law of include/gps_hip.h.
+// gps_rows_dev.h -- what gps_obj_select.hip (one thread per position, 16 waves) and gps_obj_select_pred.hip (256 threads,
+// positions strided) share: the clamp of a device-read range, the ordered compaction of up to GPS_OBJ_SELECT_MAX_SCAN
+// positions, the seeded fill law of include/gps_hip.h.  (The fill as ONE helper measured slower: profiles/rows/NOTE.md.)
 //
 // Compaction.  The positions of a scan are cut into kSegs segments of 64; a wave holds one segment at a time, lane =
 // position inside it.  seg_ballot() turns a flag into the lane's rank inside its segment (the popcount of the ballot
@@ -24,6 +24,12 @@ namespace gps_rows {
 constexpr int kMaxScan = GPS_OBJ_SELECT_MAX_SCAN;   // 1024 positions
 constexpr int kSegs = kMaxScan / 64;                // 16 segments, one wave ballot each
 
+// a [first, last) range read from device memory, clamped into [0, n) -> its length (0 for an empty or reversed one)
+__device__ __forceinline__ int clamp_range(int &first, int &last, int n) {
+  first = first < 0 ? 0 : first;
+  last = last > n ? n : last;
+  return last > first ? last - first : 0;
+}
 // -> the lane's rank among the flagged lanes of segment `seg`; cnt[seg] = how many there are (read it after a barrier)
 __device__ __forceinline__ int seg_ballot(bool flag, int *cnt, int seg, int lane) {
   const unsigned long long m = __ballot(flag);

@@ -30,6 +30,7 @@ import numpy as np
 import torch
 
 from .._launch import launch
+from ._resident import as_bool, need_finalized, need_gpu, outputs, seed_word, u64
 
 
 class PackedScans:
@@ -62,22 +63,10 @@ class PackedScans:
         assert self.xyz is None, "finalize() was already called"
         if inst_labels is not None and len(inst_labels) != len(inst_ids):
             raise ValueError("inst_labels must give one label per entry of inst_ids")
-        points = np.ascontiguousarray(points, dtype=np.float32)
-        if colors.dtype != np.uint8:
-            colors = np.ascontiguousarray(colors, dtype=np.float32)
-        if self._rgb and self._rgb[0].dtype != colors.dtype:
-            raise ValueError("all scans must store colours in the same dtype")
+        points, colors = self._arrays(points, colors)
         first = len(self._sizes)
-        kept = []
-        for n, inst in enumerate(inst_ids):
-            sel = np.flatnonzero(instance_labels == inst)
-            if sel.size == 0:
-                continue
-            self._xyz.append(points[sel])
-            self._rgb.append(np.ascontiguousarray(colors[sel]))
-            self._sizes.append(int(sel.size))
-            self._labels.append(-100 if inst_labels is None else int(inst_labels[n]))
-            kept.append(inst)
+        kept = [inst for n, inst in enumerate(inst_ids)
+                if self._append(points, colors, instance_labels == inst, -100 if inst_labels is None else inst_labels[n])]
         self._scan_objs[scan_id] = range(first, len(self._sizes))
         self._inst_ids[scan_id] = kept
 
@@ -93,24 +82,33 @@ class PackedScans:
             raise KeyError(f"add_proposals: add_scan({scan_id!r}) comes first")
         if scan_id in self._scan_props:
             raise ValueError(f"add_proposals: scan {scan_id!r} already has its proposals")
-        points = np.ascontiguousarray(points, dtype=np.float32)
-        if colors.dtype != np.uint8:
-            colors = np.ascontiguousarray(colors, dtype=np.float32)
-        if self._rgb and self._rgb[0].dtype != colors.dtype:
-            raise ValueError("all scans must store colours in the same dtype")
+        points, colors = self._arrays(points, colors)
         masks = np.asarray(masks).reshape(-1, points.shape[0])
         if len(labels) != masks.shape[0]:
             raise ValueError("add_proposals: one label per mask")
         first = len(self._sizes)
         for mask, label in zip(masks, labels):
-            sel = np.flatnonzero(mask == 1)
-            if sel.size == 0:
-                continue
-            self._xyz.append(points[sel])
-            self._rgb.append(np.ascontiguousarray(colors[sel]))
-            self._sizes.append(int(sel.size))
-            self._labels.append(int(label))
+            self._append(points, colors, mask == 1, label)
         self._scan_props[scan_id] = range(first, len(self._sizes))
+
+    def _arrays(self, points: np.ndarray, colors: np.ndarray):
+        """A scan's points as float32 and its colours as stored: uint8, or float32 for anything else; one dtype per store."""
+        if colors.dtype != np.uint8:
+            colors = np.ascontiguousarray(colors, dtype=np.float32)
+        if self._rgb and self._rgb[0].dtype != colors.dtype:
+            raise ValueError("all scans must store colours in the same dtype")
+        return np.ascontiguousarray(points, dtype=np.float32), colors
+
+    def _append(self, points: np.ndarray, colors: np.ndarray, mask: np.ndarray, label) -> bool:
+        """The points under `mask` as one more object, in `pcds[mask]` order; False (nothing stored) when there are none."""
+        sel = np.flatnonzero(mask)
+        if sel.size == 0:
+            return False
+        self._xyz.append(points[sel])
+        self._rgb.append(np.ascontiguousarray(colors[sel]))
+        self._sizes.append(int(sel.size))
+        self._labels.append(int(label))
+        return True
 
     def finalize(self) -> "PackedScans":
         sizes = np.asarray(self._sizes, dtype=np.int64)
@@ -244,23 +242,18 @@ def select_rows(packed: PackedScans, scan_ids, max_keep: int, O: Optional[int] =
     launch; `out=` accepts them too.
     'pretrain' mode is _getitem_pretrain on inst_labels_pred (base.py:227-246): the 'gt' selection over the proposals'
     ranges with their raw labels (scan_ids: the scans or their proposals' range table)."""
-    if packed.xyz is None:
-        raise RuntimeError("PackedScans.finalize() has not been called")
+    need_finalized(packed.xyz, "PackedScans")
     if mode not in _SELECT_MODES:
         raise ValueError(f"select_rows: mode {mode!r} is neither 'refer' nor 'pretrain'")
     if pc_type not in ("gt", "pred"):
         raise ValueError(f"select_rows: pc_type {pc_type!r} is neither 'gt' nor 'pred'")
     refer = mode == "refer"
     pred = pc_type == "pred"
-    if (tgt_label is not None or targets) and not (pred and refer):
+    hits = pred and refer                        # the IoU-hit crop, gps_obj_select_pred: the one branch below
+    if (tgt_label is not None or targets) and not hits:
         raise ValueError("select_rows: tgt_label and targets belong to pc_type='pred' in 'refer' mode")
-    if pred and refer:
-        return _select_rows_pred(packed, scan_ids, int(max_keep), O, tgt_obj, keep, label_map, order, seed, seed_dev, out,
-                                 tgt_label, targets)
     M = int(max_keep)
-    if O is None:
-        O = M + 1 if refer else M
-    O = int(O)
+    O = (M + 1 if refer else M) if O is None else int(O)
     if M < 1 or M > O:
         raise ValueError(f"select_rows: max_keep {M} must lie in [1, O = {O}]")
     if refer and M < 2:
@@ -269,15 +262,24 @@ def select_rows(packed: PackedScans, scan_ids, max_keep: int, O: Optional[int] =
         raise ValueError(f"select_rows: {O} object slots > {REFER_MAX_OBJ}")
     if refer and tgt_obj is None:
         raise ValueError("select_rows: 'refer' mode needs tgt_obj")
-    if keep is None:
+    if keep is None and not hits:
         raise ValueError("select_rows: keep is required (see keep_table)")
-    host_ids = not torch.is_tensor(scan_ids)
-    B = len(scan_ids)
+    # the rows' scans: ids on the host, or ready-made range tables -- for the hits a pair, annotated objects and proposals
+    if hits:
+        host_ids = not (isinstance(scan_ids, (tuple, list)) and len(scan_ids) == 2 and all(torch.is_tensor(t) for t in scan_ids))
+        if host_ids and torch.is_tensor(scan_ids):
+            raise ValueError("select_rows: pc_type='pred' takes scan ids or the pair (scan_ranges(..), scan_ranges(.., proposals=True))")
+        B = len(scan_ids) if host_ids else int(scan_ids[0].shape[0])
+    else:
+        host_ids = not torch.is_tensor(scan_ids)
+        B = len(scan_ids)
     if host_ids:
-        sizes = [len(_scan_proposals(packed, s) if pred else packed.scan_objects(s)) for s in scan_ids]
-        for sid, n in zip(scan_ids, sizes):
+        if refer:                                # what tgt_obj indexes: the annotated objects
+            sizes = [len(packed.scan_objects(s)) for s in scan_ids]
+        for sid in scan_ids:
+            n = len(_scan_proposals(packed, sid) if pred else packed.scan_objects(sid))
             if n > OBJ_SELECT_MAX_SCAN:
-                raise ValueError(f"select_rows: scan {sid} has {n} objects > {OBJ_SELECT_MAX_SCAN}")
+                raise ValueError(f"select_rows: scan {sid} has {n} {'proposals' if pred else 'objects'} > {OBJ_SELECT_MAX_SCAN}")
     tgt = None
     if refer:
         tgt = torch.as_tensor(tgt_obj).reshape(-1)
@@ -287,48 +289,61 @@ def select_rows(packed: PackedScans, scan_ids, max_keep: int, O: Optional[int] =
             raise ValueError(f"select_rows: tgt_obj must hold {B} integer positions")
         if host_ids and tgt.device.type == "cpu" and any(not 0 <= int(t) < n for t, n in zip(tgt.tolist(), sizes)):
             raise ValueError("select_rows: a target position outside its scan")
-    dev = packed.xyz.device
-    if dev.type != "cuda":
-        raise RuntimeError("select_rows runs on libgps_hip.so: scenes must live on a GPU (no CPU path)")
-    ranges = scan_ranges(packed, scan_ids, proposals=pred)
-    if refer:
-        tgt = tgt.to(device=dev, dtype=torch.int32) + ranges[:, 0]
-    if keep.dtype not in (torch.bool, torch.uint8) or keep.dim() not in (1, 2) or (keep.dim() == 2 and keep.shape[0] != B):
-        raise ValueError("select_rows: keep must be (n_labels,) or (B, n_labels) bool / uint8")
-    keep = keep.to(dev).contiguous()
-    n_labels = int(keep.shape[-1])
-    if label_map is not None:
-        if label_map.shape != (n_labels,) or label_map.dtype.is_floating_point:
-            raise ValueError(f"select_rows: label_map must hold {n_labels} integers")
-        label_map = label_map.to(device=dev, dtype=torch.int32).contiguous()
+    if tgt_label is not None:
+        tgt_label = torch.as_tensor(tgt_label).reshape(-1)
+        if tgt_label.numel() != B or tgt_label.dtype.is_floating_point or tgt_label.dtype == torch.bool:
+            raise ValueError(f"select_rows: tgt_label must hold {B} integer labels")
     R = 0
     if order is not None:
         if order.dim() != 2 or order.shape[0] != B or order.shape[1] < M or order.dtype.is_floating_point:
             raise ValueError(f"select_rows: order must be (B, R >= {M}) integers")
-        order = order.to(device=dev, dtype=torch.int32).contiguous()
         R = int(order.shape[1])
-    if seed_dev is not None and (seed_dev.device != dev or seed_dev.dtype != torch.int64 or seed_dev.numel() != 1):
-        raise ValueError("select_rows: seed_dev must be one int64 word on the scans' GPU")
-    shapes = {name: ((B, O) if name == "row_obj" else (B,)) for name, _ in _SELECT_OUT}
-    if out is not None:
-        res = {}
-        for name, dt in _SELECT_OUT:
-            t = out.get(name)
-            dtypes = (torch.bool, torch.uint8) if dt == torch.bool else (dt,)
-            if t is None or tuple(t.shape) != shapes[name] or t.dtype not in dtypes or not t.is_contiguous() or t.device != dev:
-                raise ValueError(f"select_rows: out[{name!r}] must be a contiguous {shapes[name]} {dt} tensor on the scans' GPU")
-            res[name] = t
+    dev = packed.xyz.device
+    need_gpu(dev, "select_rows", "scenes")
+    if hits:
+        ids, prop_ids = (scan_ids, scan_ids) if host_ids else scan_ids
+        ranges, props = scan_ranges(packed, ids), scan_ranges(packed, prop_ids, proposals=True)
+        if props.shape[0] != B:
+            raise ValueError("select_rows: the two range tables must have one row per batch row")
     else:
-        res = {name: torch.empty(shapes[name], dtype=dt, device=dev) for name, dt in _SELECT_OUT}
-    launch("gps_obj_select", B, O, M, _SELECT_MODES[mode], packed.n_objects, n_labels, packed.labels, ranges, tgt, keep,
-           n_labels if keep.dim() == 2 else 0, label_map, order, R, int(seed) & ((1 << 64) - 1), seed_dev,
-           res["row_obj"], res["tgt_slot"], res["n_sel"], res["n_rem"], res["is_multiple"], res["is_hard"], device=dev,
-           label=f"obj_select(B={B},O={O},M={M})", nbytes=4 * B * (O + 6) + 2 * B + 4 * B * OBJ_SELECT_MAX_SCAN // 4,
-           what="select_rows")     # outputs + ranges and target + a label per position (scans of some 256 objects)
-    for name in ("is_multiple", "is_hard"):
-        if res[name].dtype != torch.bool:
-            res[name] = res[name].bool()
-    return res
+        ranges = scan_ranges(packed, scan_ids, proposals=pred)
+    if refer:
+        tgt = tgt.to(device=dev, dtype=torch.int32) + ranges[:, 0]
+    if tgt_label is not None:
+        tgt_label = tgt_label.to(device=dev, dtype=torch.int32).contiguous()
+    n_labels = (1 << 31) - 1                     # the hits without a table: every non-negative label counts
+    if keep is not None:
+        n_labels = int(keep.shape[-1])
+    if not hits:                                 # the hits read no keep table: given, only its width counts
+        if keep.dtype not in (torch.bool, torch.uint8) or keep.dim() not in (1, 2) or (keep.dim() == 2 and keep.shape[0] != B):
+            raise ValueError("select_rows: keep must be (n_labels,) or (B, n_labels) bool / uint8")
+        keep = keep.to(dev).contiguous()
+    if label_map is not None:
+        if label_map.dim() != 1 or label_map.dtype.is_floating_point or (keep is not None and label_map.shape[0] != n_labels):
+            raise ValueError("select_rows: label_map must hold n_labels integers, as many as keep has columns")
+        n_labels = int(label_map.shape[0])
+        label_map = label_map.to(device=dev, dtype=torch.int32).contiguous()
+    if order is not None:
+        order = order.to(device=dev, dtype=torch.int32).contiguous()
+    seed_word("select_rows", seed_dev, dev, "scans")
+    spec = [(name, dt, (B, O) if name == "row_obj" else (B,)) for name, dt in _SELECT_OUT]
+    if targets:
+        spec += _refer_spec(B, O)
+    res = outputs("select_rows", spec, out, dev, "scans")
+    rows = [res[name] for name, _ in _SELECT_OUT]
+    if hits:
+        tout = [res[name] if targets else None for name, _ in _REFER_OUT]
+        launch("gps_obj_select_pred", B, O, M, packed.n_objects, n_labels, packed.boxes, packed.labels, packed.match_labels,
+               ranges, props, tgt, tgt_label, label_map, order, R, u64(seed), seed_dev, *rows, *tout,
+               device=dev, label=f"obj_select_pred(B={B},O={O},M={M})",
+               nbytes=4 * B * (O + 8) + 2 * B + (24 * B * O if targets else 0) + 52 * B * 256,
+               what="select_rows")     # outputs + ranges and target + a box and a label per position (scans of some 256 proposals)
+    else:
+        launch("gps_obj_select", B, O, M, _SELECT_MODES[mode], packed.n_objects, n_labels, packed.labels, ranges, tgt, keep,
+               n_labels if keep.dim() == 2 else 0, label_map, order, R, u64(seed), seed_dev, *rows, device=dev,
+               label=f"obj_select(B={B},O={O},M={M})", nbytes=4 * B * (O + 6) + 2 * B + 4 * B * OBJ_SELECT_MAX_SCAN // 4,
+               what="select_rows")     # outputs + ranges and target + a label per position (scans of some 256 objects)
+    return as_bool(res, ("is_multiple", "is_hard"))
 
 
 def _scan_proposals(packed: PackedScans, scan_id) -> range:
@@ -336,92 +351,6 @@ def _scan_proposals(packed: PackedScans, scan_id) -> range:
         return packed.scan_proposals(scan_id)
     except KeyError:
         raise ValueError(f"select_rows: scan {scan_id!r} has no proposals (add_proposals)") from None
-
-
-def _select_rows_pred(packed, scan_ids, M, O, tgt_obj, keep, label_map, order, seed, seed_dev, out, tgt_label, targets):
-    """`select_rows(pc_type="pred")` in 'refer' mode: one launch of gps_obj_select_pred."""
-    O = M + 1 if O is None else int(O)
-    if M < 1 or M > O:
-        raise ValueError(f"select_rows: max_keep {M} must lie in [1, O = {O}]")
-    if M < 2:
-        raise ValueError("select_rows: 'refer' mode needs max_keep >= 2")
-    if O > REFER_MAX_OBJ:
-        raise ValueError(f"select_rows: {O} object slots > {REFER_MAX_OBJ}")
-    if tgt_obj is None:
-        raise ValueError("select_rows: 'refer' mode needs tgt_obj")
-    host_ids = not (isinstance(scan_ids, (tuple, list)) and len(scan_ids) == 2 and all(torch.is_tensor(t) for t in scan_ids))
-    if host_ids and torch.is_tensor(scan_ids):
-        raise ValueError("select_rows: pc_type='pred' takes scan ids or the pair (scan_ranges(..), scan_ranges(.., proposals=True))")
-    B = len(scan_ids) if host_ids else int(scan_ids[0].shape[0])
-    if host_ids:
-        sizes = [len(packed.scan_objects(s)) for s in scan_ids]
-        for sid in scan_ids:
-            n = len(_scan_proposals(packed, sid))
-            if n > OBJ_SELECT_MAX_SCAN:
-                raise ValueError(f"select_rows: scan {sid} has {n} proposals > {OBJ_SELECT_MAX_SCAN}")
-    tgt = torch.as_tensor(tgt_obj).reshape(-1)
-    if tgt.numel() == 0:
-        tgt = tgt.to(torch.int32)
-    if tgt.numel() != B or tgt.dtype.is_floating_point or tgt.dtype == torch.bool:
-        raise ValueError(f"select_rows: tgt_obj must hold {B} integer positions")
-    if host_ids and tgt.device.type == "cpu" and any(not 0 <= int(t) < n for t, n in zip(tgt.tolist(), sizes)):
-        raise ValueError("select_rows: a target position outside its scan")
-    if tgt_label is not None:
-        tgt_label = torch.as_tensor(tgt_label).reshape(-1)
-        if tgt_label.numel() != B or tgt_label.dtype.is_floating_point or tgt_label.dtype == torch.bool:
-            raise ValueError(f"select_rows: tgt_label must hold {B} integer labels")
-    if order is not None and (order.dim() != 2 or order.shape[0] != B or order.shape[1] < M or order.dtype.is_floating_point):
-        raise ValueError(f"select_rows: order must be (B, R >= {M}) integers")
-    dev = packed.xyz.device
-    if dev.type != "cuda":
-        raise RuntimeError("select_rows runs on libgps_hip.so: scenes must live on a GPU (no CPU path)")
-    if host_ids:
-        ranges, props = scan_ranges(packed, scan_ids), scan_ranges(packed, scan_ids, proposals=True)
-    else:
-        ranges, props = scan_ranges(packed, scan_ids[0]), scan_ranges(packed, scan_ids[1])
-        if props.shape[0] != B:
-            raise ValueError("select_rows: the two range tables must have one row per batch row")
-    tgt = tgt.to(device=dev, dtype=torch.int32) + ranges[:, 0]
-    if tgt_label is not None:
-        tgt_label = tgt_label.to(device=dev, dtype=torch.int32).contiguous()
-    n_labels = (1 << 31) - 1                     # without a table every non-negative label counts
-    if keep is not None:
-        n_labels = int(keep.shape[-1])
-    if label_map is not None:
-        if label_map.dim() != 1 or label_map.dtype.is_floating_point or (keep is not None and label_map.shape[0] != n_labels):
-            raise ValueError("select_rows: label_map must hold n_labels integers")
-        n_labels = int(label_map.shape[0])
-        label_map = label_map.to(device=dev, dtype=torch.int32).contiguous()
-    R = 0
-    if order is not None:
-        order = order.to(device=dev, dtype=torch.int32).contiguous()
-        R = int(order.shape[1])
-    if seed_dev is not None and (seed_dev.device != dev or seed_dev.dtype != torch.int64 or seed_dev.numel() != 1):
-        raise ValueError("select_rows: seed_dev must be one int64 word on the scans' GPU")
-    spec = [(name, dt, (B, O) if name == "row_obj" else (B,)) for name, dt in _SELECT_OUT]
-    if targets:
-        spec += [(name, torch.int64, (B, w if w is not None else O)) for name, w in _REFER_OUT]
-    res = {}
-    for name, dt, shape in spec:
-        if out is None:
-            res[name] = torch.empty(shape, dtype=dt, device=dev)
-            continue
-        t = out.get(name)
-        dtypes = (torch.bool, torch.uint8) if dt == torch.bool else (dt,)
-        if t is None or tuple(t.shape) != shape or t.dtype not in dtypes or not t.is_contiguous() or t.device != dev:
-            raise ValueError(f"select_rows: out[{name!r}] must be a contiguous {shape} {dt} tensor on the scans' GPU")
-        res[name] = t
-    tout = [res[name] if targets else None for name, _ in _REFER_OUT]
-    launch("gps_obj_select_pred", B, O, M, packed.n_objects, n_labels, packed.boxes, packed.labels, packed.match_labels,
-           ranges, props, tgt, tgt_label, label_map, order, R, int(seed) & ((1 << 64) - 1), seed_dev,
-           res["row_obj"], res["tgt_slot"], res["n_sel"], res["n_rem"], res["is_multiple"], res["is_hard"], *tout,
-           device=dev, label=f"obj_select_pred(B={B},O={O},M={M})",
-           nbytes=4 * B * (O + 8) + 2 * B + (24 * B * O if targets else 0) + 52 * B * 256,
-           what="select_rows")     # outputs + ranges and target + a box and a label per position (scans of some 256 proposals)
-    for name in ("is_multiple", "is_hard"):
-        if res[name].dtype != torch.bool:
-            res[name] = res[name].bool()
-    return res
 
 
 def obj_processing_post(packed: PackedScans, row_obj: torch.Tensor, num_points: int = 1024,
@@ -437,47 +366,52 @@ def obj_processing_post(packed: PackedScans, row_obj: torch.Tensor, num_points: 
     out: optional {"obj_fts", "obj_locs", "obj_masks"} of preallocated contiguous tensors of those shapes (obj_masks bool
     or uint8) the kernel writes IN PLACE -- the static input buffers of a captured training step
     (`GPSTrainStep.static_inputs()`), so that no per-step copy of the 126 MB of object points is needed."""
-    if packed.xyz is None:
-        raise RuntimeError("PackedScans.finalize() has not been called")
-    dev = packed.xyz.device
-    if dev.type != "cuda":
-        raise RuntimeError("obj_processing_post runs on libgps_hip.so: scenes must live on a GPU (no CPU path)")
+    dev = _obj_device(packed, "obj_processing_post")
     B, O = row_obj.shape
     n_rows = B * O
     nbytes = _algorithmic_bytes(packed, row_obj if row_obj.device.type == "cpu" else None, n_rows, num_points)
-    row_obj = row_obj.to(device=dev, dtype=torch.int32).contiguous()
-    if out is not None:
-        fts, locs, masks = out["obj_fts"], out["obj_locs"], out["obj_masks"]
-        ok = (fts.shape == (B, O, num_points, 6) and fts.dtype == torch.float32 and locs.shape == (B, O, 6)
-              and locs.dtype == torch.float32 and masks.shape == (B, O) and masks.dtype in (torch.bool, torch.uint8)
-              and all(t.is_contiguous() and t.device == dev for t in (fts, locs, masks)))
-        if not ok:
-            raise ValueError("obj_processing_post: `out` tensors must be contiguous (B,O,P,6) f32 / (B,O,6) f32 / (B,O) bool on the scans' GPU")
-    else:
-        fts = torch.empty((B, O, num_points, 6), dtype=torch.float32, device=dev)
-        locs = torch.empty((B, O, 6), dtype=torch.float32, device=dev)
-        masks = torch.empty((B, O), dtype=torch.uint8, device=dev)
-    boxes = torch.empty((B, O, 6), dtype=torch.float32, device=dev) if need_boxes else None
+    row_obj, sample_idx, res = _obj_buffers("obj_processing_post", row_obj, num_points, sample_idx, need_boxes, out, dev)
     rot_t = row_rot = None
     if rot is not None:
         rot_t, row_rot = rot_rows(rot, B, O, dev)
+    launch("gps_obj_processing_post", n_rows, num_points, packed.xyz, packed.rgb,
+           int(packed.rgb is None or packed.rgb.dtype == torch.uint8), packed.obj_offsets, row_obj, sample_idx,
+           u64(seed), rot_t, row_rot, res["obj_fts"], res["obj_locs"], res.get("obj_boxes"), res["obj_masks"], device=dev,
+           label=f"obj_processing_post(rows={n_rows},P={num_points})", nbytes=nbytes, what="obj_processing_post")
+    return as_bool(res, ("obj_masks",))
+
+
+def _obj_device(packed: PackedScans, what: str) -> torch.device:
+    """The two guards of a call that checks nothing on the host between them -> the scans' GPU."""
+    need_finalized(packed.xyz, "PackedScans")
+    need_gpu(packed.xyz.device, what, "scenes")
+    return packed.xyz.device
+
+
+def _obj_buffers(what: str, row_obj: torch.Tensor, num_points: int, sample_idx, need_boxes: bool, out, dev):
+    """What obj_processing_post and obj_processing_aug share past their guards -> (the row table and the replayed sample
+    indices as the launch reads them, the result dict: `out`'s tensors or new ones, obj_boxes always new)."""
+    B, O = row_obj.shape
+    row_obj = row_obj.to(device=dev, dtype=torch.int32).contiguous()
     if sample_idx is not None:
         sample_idx = sample_idx.to(device=dev, dtype=torch.int32).contiguous()
         assert sample_idx.shape == (B, O, num_points), sample_idx.shape
-    launch("gps_obj_processing_post", n_rows, num_points, packed.xyz, packed.rgb,
-           int(packed.rgb is None or packed.rgb.dtype == torch.uint8), packed.obj_offsets, row_obj, sample_idx,
-           int(seed) & ((1 << 64) - 1), rot_t, row_rot, fts, locs, boxes, masks, device=dev,
-           label=f"obj_processing_post(rows={n_rows},P={num_points})", nbytes=nbytes, what="obj_processing_post")
-    res = {"obj_fts": fts, "obj_locs": locs, "obj_masks": masks if masks.dtype == torch.bool else masks.bool()}
+    res = outputs(what, (("obj_fts", torch.float32, (B, O, num_points, 6)), ("obj_locs", torch.float32, (B, O, 6)),
+                         ("obj_masks", torch.uint8, (B, O))), out, dev, "scans")
     if need_boxes:
-        res["obj_boxes"] = boxes
-    return res
+        res["obj_boxes"] = torch.empty((B, O, 6), dtype=torch.float32, device=dev)
+    return row_obj, sample_idx, res
 
 
 # ---- ScanRefer targets: boxes of every object, IoU flags per batch ---------------------------------------------
 BOXES_CHUNK = 4096                               # GPS_OBJ_BOXES_CHUNK of include/gps_hip.h
 REFER_MAX_OBJ = 512                              # GPS_REFER_MAX_OBJ
 _REFER_OUT = (("tgt_object_id_iou25", None), ("tgt_object_id_iou50", None), ("tgt_object_id", 1), ("obj_labels", None))
+
+
+def _refer_spec(B: int, O: int) -> list:
+    """(name, dtype, shape) of the four target tensors, for `outputs`."""
+    return [(name, torch.int64, (B, O if w is None else w)) for name, w in _REFER_OUT]
 
 
 def boxes_work_list(sizes: np.ndarray, chunk: int = BOXES_CHUNK) -> np.ndarray:
@@ -502,11 +436,7 @@ def obj_boxes(packed: PackedScans) -> torch.Tensor:
     """convert_pc_to_box (data/data_utils.py:63-72) of every packed object, annotated and proposal, in one pass:
     (n_objects, 6) float64 [centre, size], bit-equal to numpy on the loader's float64 rows.  finalize() calls it once
     and keeps the result as `packed.boxes`."""
-    if packed.xyz is None:
-        raise RuntimeError("PackedScans.finalize() has not been called")
-    dev = packed.xyz.device
-    if dev.type != "cuda":
-        raise RuntimeError("obj_boxes runs on libgps_hip.so: scenes must live on a GPU (no CPU path)")
+    dev = _obj_device(packed, "obj_boxes")
     n = packed.n_objects
     boxes = torch.empty((n, 6), dtype=torch.float64, device=dev)
     if n == 0:
@@ -524,11 +454,7 @@ def proposal_labels(packed: PackedScans) -> torch.Tensor:
     on the scan only, so finalize() computes it once (one launch over all proposals) and keeps it as
     `packed.match_labels`: what `select_rows(pc_type="pred")` reads, bit-equal to `refer_targets(..., "pred")`'s
     obj_labels for every proposal."""
-    if packed.xyz is None:
-        raise RuntimeError("PackedScans.finalize() has not been called")
-    dev = packed.xyz.device
-    if dev.type != "cuda":
-        raise RuntimeError("proposal_labels runs on libgps_hip.so: scenes must live on a GPU (no CPU path)")
+    dev = _obj_device(packed, "proposal_labels")
     match = packed.labels.clone()
     ids, ann = [], []
     for sid, props in packed._scan_props.items():
@@ -559,8 +485,7 @@ def refer_targets(packed: PackedScans, row_obj: torch.Tensor, tgt_obj, scan_ids:
     (pad_tensors asserts); a row table on the host is checked for that here (ValueError), one on the device is not.
     Integer-stored colours: bit-equal flags; float32-stored colours: the float64 form still (the reference's float32
     boxes are no parity target).  `is_multiple` / `is_hard` are dictionary look-ups of the caller, or `select_rows`'."""
-    if packed.xyz is None:
-        raise RuntimeError("PackedScans.finalize() has not been called")
+    need_finalized(packed.xyz, "PackedScans")
     if pc_type not in ("pred", "gt"):
         raise ValueError(f"refer_targets: pc_type {pc_type!r} is neither 'pred' nor 'gt'")
     B, O = row_obj.shape
@@ -571,19 +496,11 @@ def refer_targets(packed: PackedScans, row_obj: torch.Tensor, tgt_obj, scan_ids:
     if row_obj.device.type == "cpu" and B and bool((row_obj[:, -1] >= 0).any()):
         raise ValueError("refer_targets: a scene fills all object slots; the targets need max_obj_len >= n_objects + 1")
     dev = packed.xyz.device
-    if dev.type != "cuda":
-        raise RuntimeError("refer_targets runs on libgps_hip.so: scenes must live on a GPU (no CPU path)")
+    need_gpu(dev, "refer_targets", "scenes")
     row_obj = row_obj.to(device=dev, dtype=torch.int32).contiguous()
     ranges = scan_ranges(packed, scan_ids)
     tgt = torch.as_tensor(tgt_obj).reshape(B).to(device=dev, dtype=torch.int32) + ranges[:, 0]
-    shapes = {name: (B, w if w is not None else O) for name, w in _REFER_OUT}
-    if out is not None:
-        res = {name: out[name] for name, _ in _REFER_OUT}
-        if not all(t.shape == shapes[n] and t.dtype == torch.int64 and t.is_contiguous() and t.device == dev
-                   for n, t in res.items()):
-            raise ValueError("refer_targets: `out` tensors must be contiguous int64 (B,O) / (B,1) on the scans' GPU")
-    else:
-        res = {name: torch.empty(shapes[name], dtype=torch.int64, device=dev) for name, _ in _REFER_OUT}
+    res = outputs("refer_targets", _refer_spec(B, O), out, dev, "scans")
     launch("gps_refer_targets", B, O, packed.n_objects, int(pc_type == "gt"), packed.boxes, packed.labels, row_obj, tgt, ranges,
            res["tgt_object_id_iou25"], res["tgt_object_id_iou50"], res["tgt_object_id"], res["obj_labels"], device=dev)
     return res
@@ -687,11 +604,7 @@ def obj_processing_aug(packed: PackedScans, row_obj: torch.Tensor, num_points: i
     sample_idx (B,O,num_points) int32 / jitter_noise (B,O,num_points,3) float32 or float64: the reference's
     np.random.choice / np.random.randn draws for a replay -- already in the order the point shuffle left them; None =
     drawn on the device from `seed` (the noise only for scenes whose obj_jitter is set)."""
-    if packed.xyz is None:
-        raise RuntimeError("PackedScans.finalize() has not been called")
-    dev = packed.xyz.device
-    if dev.type != "cuda":
-        raise RuntimeError("obj_processing_aug runs on libgps_hip.so: scenes must live on a GPU (no CPU path)")
+    dev = _obj_device(packed, "obj_processing_aug")
     B, O = row_obj.shape
     n_rows = B * O
     if isinstance(aug, AugParams):
@@ -703,22 +616,7 @@ def obj_processing_aug(packed: PackedScans, row_obj: torch.Tensor, num_points: i
         tab = row_aug = None
     nbytes = _algorithmic_bytes(packed, row_obj if row_obj.device.type == "cpu" else None, n_rows, num_points,
                                 stream_all=scaled)
-    row_obj = row_obj.to(device=dev, dtype=torch.int32).contiguous()
-    if out is not None:
-        fts, locs, masks = out["obj_fts"], out["obj_locs"], out["obj_masks"]
-        ok = (fts.shape == (B, O, num_points, 6) and fts.dtype == torch.float32 and locs.shape == (B, O, 6)
-              and locs.dtype == torch.float32 and masks.shape == (B, O) and masks.dtype in (torch.bool, torch.uint8)
-              and all(t.is_contiguous() and t.device == dev for t in (fts, locs, masks)))
-        if not ok:
-            raise ValueError("obj_processing_aug: `out` tensors must be contiguous (B,O,P,6) f32 / (B,O,6) f32 / (B,O) bool on the scans' GPU")
-    else:
-        fts = torch.empty((B, O, num_points, 6), dtype=torch.float32, device=dev)
-        locs = torch.empty((B, O, 6), dtype=torch.float32, device=dev)
-        masks = torch.empty((B, O), dtype=torch.uint8, device=dev)
-    boxes = torch.empty((B, O, 6), dtype=torch.float32, device=dev) if need_boxes else None
-    if sample_idx is not None:
-        sample_idx = sample_idx.to(device=dev, dtype=torch.int32).contiguous()
-        assert sample_idx.shape == (B, O, num_points), sample_idx.shape
+    row_obj, sample_idx, res = _obj_buffers("obj_processing_aug", row_obj, num_points, sample_idx, need_boxes, out, dev)
     if jitter_noise is not None:
         if jitter_noise.dtype not in (torch.float32, torch.float64):
             raise ValueError("obj_processing_aug: jitter_noise must be float32 or float64")
@@ -726,13 +624,11 @@ def obj_processing_aug(packed: PackedScans, row_obj: torch.Tensor, num_points: i
         assert jitter_noise.shape == (B, O, num_points, 3), jitter_noise.shape
     launch("gps_obj_processing_aug", n_rows, num_points, packed.xyz, packed.rgb,
            int(packed.rgb is None or packed.rgb.dtype == torch.uint8), packed.obj_offsets, row_obj, sample_idx, jitter_noise,
-           int(jitter_noise is not None and jitter_noise.dtype == torch.float64), int(seed) & ((1 << 64) - 1),
-           tab, row_aug, tab.shape[0] if tab is not None else 0, fts, locs, boxes, masks,
-           device=dev, label=f"obj_processing_aug(rows={n_rows},P={num_points})", nbytes=nbytes, what="obj_processing_aug")
-    res = {"obj_fts": fts, "obj_locs": locs, "obj_masks": masks if masks.dtype == torch.bool else masks.bool()}
-    if need_boxes:
-        res["obj_boxes"] = boxes
-    return res
+           int(jitter_noise is not None and jitter_noise.dtype == torch.float64), u64(seed),
+           tab, row_aug, tab.shape[0] if tab is not None else 0, res["obj_fts"], res["obj_locs"], res.get("obj_boxes"),
+           res["obj_masks"], device=dev, label=f"obj_processing_aug(rows={n_rows},P={num_points})", nbytes=nbytes,
+           what="obj_processing_aug")
+    return as_bool(res, ("obj_masks",))
 
 
 def _check_key(key) -> bool:

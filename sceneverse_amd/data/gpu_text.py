@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from .._launch import launch
+from ._resident import as_bool, need_finalized, need_gpu, outputs, seed_word, u64
 
 BERT_SPECIAL = (101, 102, 103, 0)                # [CLS], [SEP], [MASK], [PAD]
 BERT_VOCAB = 30522
@@ -109,11 +110,9 @@ def text_batch(texts: PackedTexts, sent_idx, cap_idx=None, *, max_seq_len: int =
     written IN PLACE -- the static input buffers of a captured training step (`GPSTrainStep.static_inputs()`), exactly as
     `obj_processing_post(out=)`.  Text ids that arrive on the host are range-checked there (ValueError); on the device,
     an id out of range reads as an empty text."""
-    if texts.tok is None:
-        raise RuntimeError("PackedTexts.finalize() has not been called")
+    need_finalized(texts.tok, "PackedTexts")
     dev = texts.tok.device
-    if dev.type != "cuda":
-        raise RuntimeError("text_batch runs on libgps_hip.so: texts must live on a GPU (no CPU path)")
+    need_gpu(dev, "text_batch", "texts")
     L, Ls = int(max_seq_len), int(max_scene_cap_len)
     sent = _index("sent_idx", sent_idx, texts.n_texts, dev)
     shape = tuple(sent.shape)
@@ -142,27 +141,16 @@ def text_batch(texts: PackedTexts, sent_idx, cap_idx=None, *, max_seq_len: int =
             if draws.u_obj is None or tuple(draws.u_obj.shape) != tuple(obj_masks.shape):
                 raise ValueError("text_batch: draws.u_obj must have the shape of obj_masks")
             u_obj = draws.u_obj.to(device=dev, dtype=torch.float64).contiguous()
-    if seed_dev is not None and (seed_dev.device != dev or seed_dev.dtype != torch.int64 or seed_dev.numel() != 1):
-        raise ValueError("text_batch: seed_dev must be one int64 word on the texts' GPU")
+    seed_word("text_batch", seed_dev, dev, "texts")
 
-    want = {"txt_ids": shape + (L,), "txt_masks": shape + (L,)}
+    spec = [("txt_ids", torch.int64, shape + (L,)), ("txt_masks", torch.int64, shape + (L,))]
     if mask or (out is not None and "masked_lm_labels" in out):
-        want["masked_lm_labels"] = shape + (L,)
+        spec.append(("masked_lm_labels", torch.int64, shape + (L,)))
     if cap is not None:
-        want["scene_txt_ids"] = want["scene_txt_masks"] = shape + (Ls,)
+        spec += [("scene_txt_ids", torch.int64, shape + (Ls,)), ("scene_txt_masks", torch.int64, shape + (Ls,))]
     if obj_masks is not None:
-        want["obj_sem_masks"] = tuple(obj_masks.shape)
-    if out is not None:
-        res = {}
-        for name, shp in want.items():
-            t = out.get(name)
-            dtypes = (torch.bool, torch.uint8) if name == "obj_sem_masks" else (torch.int64,)
-            if t is None or tuple(t.shape) != shp or t.dtype not in dtypes or not t.is_contiguous() or t.device != dev:
-                raise ValueError(f"text_batch: out[{name!r}] must be a contiguous {shp} {dtypes[0]} tensor on the texts' GPU")
-            res[name] = t
-    else:
-        res = {name: torch.empty(shp, dtype=torch.bool if name == "obj_sem_masks" else torch.int64, device=dev)
-               for name, shp in want.items()}
+        spec.append(("obj_sem_masks", torch.bool, tuple(obj_masks.shape)))
+    res = outputs("text_batch", spec, out, dev, "texts")
     cls_id, sep_id, mask_id, pad_id = (int(x) for x in special)
     # every output written once + at most one token read per position + the object flags read
     nbytes = (sum(t.numel() * t.element_size() for t in res.values()) + 4 * n_rows * (L + (Ls if cap is not None else 0))
@@ -170,9 +158,7 @@ def text_batch(texts: PackedTexts, sent_idx, cap_idx=None, *, max_seq_len: int =
     launch("gps_text_batch", texts.n_texts, int(texts.tok.numel()), texts.tok, texts.off, n_rows, sent, cap, L, Ls,
            _NO_CAP if scene_sent_cap is None else int(scene_sent_cap), cls_id, sep_id, mask_id, pad_id, int(vocab_size),
            int(bool(mask)), float(txt_mask_ratio), float(pc_mask_ratio), n_obj_rows, O, obj_masks, u_tok, rand_tok, u_obj,
-           int(seed) & ((1 << 64) - 1), seed_dev, res["txt_ids"], res["txt_masks"], res.get("masked_lm_labels"),
+           u64(seed), seed_dev, res["txt_ids"], res["txt_masks"], res.get("masked_lm_labels"),
            res.get("scene_txt_ids"), res.get("scene_txt_masks"), res.get("obj_sem_masks"), device=dev,
            label=f"text_batch(rows={n_rows},L={L},Ls={Ls if cap is not None else 0})", nbytes=nbytes, what="text_batch")
-    if "obj_sem_masks" in res and res["obj_sem_masks"].dtype != torch.bool:
-        res["obj_sem_masks"] = res["obj_sem_masks"].bool()
-    return res
+    return as_bool(res, ("obj_sem_masks",))
