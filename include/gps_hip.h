@@ -941,6 +941,74 @@ GPS_API int gps_cls_hits(const gps_cls_hits_problem *problems, int n_problems, g
 GPS_API int gps_metrics_fold(int n_terms, const gps_metric_term *terms, double weight, int n_mean, double *last,
                              double *acc, double *total, gps_stream_t stream);
 
+/* ---- answer accuracy of the ScanQA and SQA3D evaluators: ranked top-k ------------------------------------
+ * Replaces the argmax / topk / per-question label look-ups of ScanQAEval.batch_metrics (evaluator/scanqa_eval.py:29-45)
+ * and SQA3DEval.batch_metrics (evaluator/sqa3d_eval.py:78-116), and the bookkeeping of BaseEvaluator.update / record
+ * (evaluator/build.py:26-41) and SQA3DEval.update / record / reset (evaluator/sqa3d_eval.py:49-76, 118-137).
+ *
+ * THE RANKING LAW (the order of `Best::beats` in csrc/gps_metrics.hip, the one gps_cls_hits takes its arg-max by):
+ *   NaN ranks above every number; then the value, descending, with -0.0 == +0.0; among equals the LOWER column comes
+ *   first.  Place 0 is torch.argmax; place j is the best answer that place j-1 beats.  Where a row's k best values are
+ *   distinct this is torch.topk; where they are not, torch.topk promises no order and the reference's ans10_acc depends
+ *   on which implementation ran -- here it does not.
+ *
+ * gps_answer_hits: ONE launch per batch.  scores (rows, ld >= cols) f32 or (scores_bf16 != 0) bf16, element-aligned,
+ *   rows at ANY element alignment; label (rows, ld_label >= cols) multi-hot, label_kind 0: int64, 1: uint8 / bool,
+ *   2: f32 -- an entry counts iff it EQUALS 1 (the reference's `== 1`); type: optional (rows) int64 question types with
+ *   n_types <= GPS_ANSWER_MAX_TYPES; rows_dev: optional device int32, rows at or past *rows_dev are dead (not read, not
+ *   counted, their topk rows not written); 1 <= k <= GPS_ANSWER_MAX_K; topk: optional (rows, k) int32, the row's k best
+ *   answer ids in rank order, -1 in the places past cols when cols < k; words: GPS_ANSWER_WORDS int64.  The launch ADDS
+ *     words[0] += rows whose label is 1 at place 0            (ans1)
+ *     words[1] += rows whose label is 1 at one of the first min(k, cols) places   (ans-k)
+ *     words[2] += live rows
+ *     words[3 + t]  += place-0 hits of the rows of type t,  words[11 + t] += rows of type t      (0 <= t < n_types)
+ *   A row whose type is outside [0, n_types) counts in words[0..2] only.  Of the label only the (at most k) entries at
+ *   the ranked ids of a live row are read; of the scores no load leaves [row * ld, row * ld + cols) of a live row.
+ *   Rows of cols <= GPS_ANSWER_WAVE_MAX_COLS take one wave each, wider rows one 256-thread workgroup each; every place
+ *   is one more pass over the row (no sort, no per-thread array, no limit on cols).  Integer atomics only, one per
+ *   non-zero word per workgroup.  Checked before any HIP call: a NULL args / scores / label / words pointer, rows < 0,
+ *   cols <= 0, ld or ld_label < cols, k outside 1..GPS_ANSWER_MAX_K, n_types outside 0..GPS_ANSWER_MAX_TYPES, label_kind
+ *   outside 0..2, misaligned scores: GPS_ERR_INVALID_ARGUMENT.  rows == 0: GPS_OK, nothing launched.
+ *
+ * gps_answer_fold: one tiny launch that turns the batch words (and up to GPS_ANSWER_FOLD_MAX_CLS gps_cls_hits counter
+ *   rows, cls_words (n_cls, 6): hits = [i][0], count = [i][1]) into bookkeeping, clears them, and keeps running sums.
+ *   One rounding per operation, additions left to right.
+ *   sums != NULL -- the integer pairs of ScanQAEval / BaseEvaluator: pairs (words[0], words[2]), (words[1], words[2]),
+ *     then (hits, count) of each cls row; per pair p: sums[2p] += h, sums[2p + 1] += c, last[p] = h / max(c, 1).
+ *     last: 2 + n_cls doubles; acc, type_total, total unused (may be NULL); weight, n_types ignored.
+ *   sums == NULL -- the float64 bookkeeping of SQA3DEval (n_cls <= 1), weight = float(B):
+ *     ans1 = words[0] / weight, ansk = words[1] / weight, obj = cls hits / (double)cls count -- the reference divides by
+ *     zero for a batch without a masked object (sqa3d_eval.py:105-107); that case is DEFINED AS 0 here, as is n_cls == 0;
+ *     per type t: ct = (((1e-10 + 1) + 1) + ...) with words[11 + t] ones (sqa3d_eval.py:87-89: a sequential chain, not
+ *     n_t + 1e-10), acc_t = words[3 + t] / ct.
+ *     last = [target_metric (= ans1), obj, ans1, ansk, acc_0 .. acc_{n_types-1}, ct_0 .. ct_{n_types-1}]
+ *     acc[i] += last[i] * weight for i < 4;  acc[4 + t] += acc_t * ct;  type_total[t] += ct;  total[0] += weight.
+ *     The caller starts type_total at the reference's 1e-10 (it gains another 1e-10 per batch, as the reference's does).
+ *   Checked before any HIP call: NULL words / last, n_cls outside 0..GPS_ANSWER_FOLD_MAX_CLS or without cls_words, and
+ *   with sums == NULL a NULL acc / type_total / total, n_cls > 1, n_types outside 0..GPS_ANSWER_MAX_TYPES, weight <= 0:
+ *   GPS_ERR_INVALID_ARGUMENT. */
+#define GPS_ANSWER_MAX_K 16
+#define GPS_ANSWER_MAX_TYPES 8
+#define GPS_ANSWER_WORDS 19
+#define GPS_ANSWER_WAVE_MAX_COLS 64
+#define GPS_ANSWER_FOLD_MAX_CLS 8
+typedef struct gps_answer_hits_args {
+  int rows, cols;
+  const void *scores;
+  long long ld;
+  int scores_bf16, label_kind;
+  const void *label;
+  long long ld_label;
+  const int64_t *type;
+  int n_types, k;
+  const int32_t *rows_dev;
+  int32_t *topk;
+  int64_t *words;
+} gps_answer_hits_args;
+GPS_API int gps_answer_hits(const gps_answer_hits_args *args, gps_stream_t stream);
+GPS_API int gps_answer_fold(int64_t *words, int64_t *cls_words, int n_cls, int n_types, double weight, int64_t *sums,
+                            double *last, double *acc, double *type_total, double *total, gps_stream_t stream);
+
 /* ---- bias gradients: column sums of a bf16 matrix ---------------------------------------------------
  * Replaces the `dY.sum(0)` autograd derives for the bias of every nn.Linear in the transformer stacks
  * (modules/layers/transformers.py:115-154, 285-316; HF BertLayer behind modules/language/bert.py:21-26).

@@ -82,7 +82,15 @@ class MetricTerm(ctypes.Structure):
                 ("const_denominator", ctypes.c_double), ("use_const_denominator", _i), ("reserved", _i)]
 
 
+class AnswerHitsArgs(ctypes.Structure):
+    """struct gps_answer_hits_args of include/gps_hip.h, field for field."""
+    _fields_ = [("rows", _i), ("cols", _i), ("scores", _vp), ("ld", ctypes.c_longlong), ("scores_bf16", _i),
+                ("label_kind", _i), ("label", _vp), ("ld_label", ctypes.c_longlong), ("type", _vp), ("n_types", _i),
+                ("k", _i), ("rows_dev", _vp), ("topk", _vp), ("words", _vp)]
+
+
 CLS_HITS_MAX_PROBLEMS, CLS_HITS_WAVE_MAX_COLS, METRICS_MAX_TERMS = 8, 1024, 16
+ANSWER_MAX_K, ANSWER_MAX_TYPES, ANSWER_WORDS, ANSWER_WAVE_MAX_COLS, ANSWER_FOLD_MAX_CLS = 16, 8, 19, 64, 8
 ATTN_BF16, ATTN_F32 = 0, 1
 ATTN_COMPUTE_NATIVE, ATTN_COMPUTE_FP8 = 0, 1
 GEMM_NT, GEMM_NN, GEMM_TN = 0, 1, 2
@@ -155,6 +163,8 @@ SIGNATURES = {
     "gps_obj_select_pred": [_i] * 5 + [_vp] * 9 + [_i, ctypes.c_ulonglong] + [_vp] * 12,
     "gps_cls_hits": [ctypes.POINTER(ClsHitsProblem), _i, _vp],
     "gps_metrics_fold": [_i, ctypes.POINTER(MetricTerm), ctypes.c_double, _i, _vp, _vp, _vp, _vp],
+    "gps_answer_hits": [ctypes.POINTER(AnswerHitsArgs), _vp],
+    "gps_answer_fold": [_vp, _vp, _i, _i, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp],
     "gps_embedding_grad_scratch_ints": [_i, _i, _i],
     "gps_embedding_grad": [_i, _i, _i, _vp, _vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, _vp],
     "gps_loc_embed_partial_rows": [_i],

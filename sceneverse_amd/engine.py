@@ -164,12 +164,19 @@ class GPSTrainStep:
         # tests / diagnostics: called with a stage name at the capture / replay points of the split-graph step
         self.stage_hook = None
         # train_metrics: False (default: the step's launches, outputs and graphs are untouched), True, or the names of the
-        # PretrainCounter keys to compute.  The reference's trainer calls evaluator["train"].batch_metrics on every
-        # training step (trainer/default_trainer.py); here the counts stay on the device: the update is issued behind
+        # PretrainCounter keys to compute; "scanqa" / "sqa3d" for a ScanQACounter / SQA3DCounter on the QA fine-tune, or a
+        # counter instance (anything with update(out) and last()).  The reference's trainer calls
+        # evaluator["train"].batch_metrics on every training step (trainer/default_trainer.py); here the counts stay on the device: the update is issued behind
         # the losses, inside whatever graph holds them, and `train_metrics()` hands out the last step's ratios.
         self.metric_counter = None
         self.metrics_hook = None              # tests: called as hook(engine, out) right before the counter's update
-        if train_metrics is not False and train_metrics is not None:
+        if isinstance(train_metrics, str):
+            if train_metrics not in ("scanqa", "sqa3d"):
+                raise ValueError(f"train_metrics: {train_metrics!r} is neither 'scanqa' nor 'sqa3d'")
+            self.metric_counter = (ScanQACounter if train_metrics == "scanqa" else SQA3DCounter)(self.device)
+        elif hasattr(train_metrics, "update") and hasattr(train_metrics, "last"):
+            self.metric_counter = train_metrics
+        elif train_metrics is not False and train_metrics is not None:
             self.metric_counter = PretrainCounter(self.device, keys=None if train_metrics is True else train_metrics)
         if self.graph_dp and dist_utils.is_dist():
             with torch.no_grad():                      # what DDP does at construction
@@ -623,7 +630,7 @@ class GPSTrainStep:
     def _metrics_sink(self):
         """Around a loss evaluation: the fused masked-LM loss adds its hit count to the metric counter's words."""
         c = self.metric_counter
-        if c is None or not self.net.training or not c._wanted("lang_cls_acc_mask"):
+        if not isinstance(c, PretrainCounter) or not self.net.training or not c._wanted("lang_cls_acc_mask"):
             return contextlib.nullcontext()
         return c.sink()
 
@@ -637,7 +644,7 @@ class GPSTrainStep:
             self.metric_counter.update(out)
 
     def train_metrics(self) -> dict:
-        """The last step's pre-train accuracies ({key: 0-dim float64 device tensor}; no host sync); needs
+        """The last step's accuracies of the metric counter ({key: 0-dim float64 device tensor}; no host sync); needs
         `train_metrics=` at construction.  `metric_counter.result()` gives the running averages."""
         if self.metric_counter is None:
             raise RuntimeError("GPSTrainStep was built without train_metrics")
@@ -1090,7 +1097,8 @@ def _answer_hits(answer_scores: torch.Tensor, answer_label: torch.Tensor, k: int
 def scanqa_accuracy(answer_scores: torch.Tensor, answer_label: torch.Tensor) -> dict:
     """ans1_acc / ans10_acc exactly as the reference's ScanQAEval.batch_metrics counts them
     (evaluator/scanqa_eval.py:29-45 and its division by max(count, 1) at :77-79): a question counts when the multi-hot
-    `answer_label` is set at the arg-max answer / at one of the ten best answers."""
+    `answer_label` is set at the arg-max answer / at one of the ten best answers.  Among equal scores torch.topk
+    promises no order; `ScanQACounter` ranks ties by the stated law (include/gps_hip.h) and agrees where there are none."""
     hit1, hit10 = _answer_hits(answer_scores, answer_label)
     n = max(answer_scores.shape[0], 1)
     return {"ans1_acc": hit1.sum().item() / n, "ans10_acc": hit10.sum().item() / n}
@@ -1099,7 +1107,8 @@ def scanqa_accuracy(answer_scores: torch.Tensor, answer_label: torch.Tensor) -> 
 def sqa3d_accuracy(answer_scores: torch.Tensor, answer_label: torch.Tensor, sqa_type: torch.Tensor) -> dict:
     """ans1_acc / ans10_acc plus type{0..5}_acc and type{0..5}_count as the reference's SQA3DEval.batch_metrics returns
     them (evaluator/sqa3d_eval.py:78-116): the per-type counts start at its 1e-10 floor, so an absent question type gives
-    accuracy 0 and not a division by zero."""
+    accuracy 0 and not a division by zero.  Among equal scores torch.topk promises no order; `SQA3DCounter` ranks ties by
+    the stated law (include/gps_hip.h) and agrees where there are none."""
     hit1, hit10 = _answer_hits(answer_scores, answer_label)
     n = float(answer_scores.shape[0])
     types = sqa_type.reshape(-1).to(torch.int64)
@@ -1115,6 +1124,158 @@ def sqa3d_accuracy(answer_scores: torch.Tensor, answer_label: torch.Tensor, sqa_
     out["target_metric"] = out["ans1_acc"]
     out["total_count"] = answer_scores.shape[0]
     return out
+
+
+class _AnswerCounter:
+    """What ScanQACounter and SQA3DCounter share: the batch words of gps_answer_hits, the counter rows of the object-class
+    gps_cls_hits problems, and the optional (B, 10) ranked answer ids of the last batch."""
+    K = 10
+    _MAX_CLS = 1
+
+    def __init__(self, device: torch.device | str = "cuda", topk: bool = False):
+        from .common import answer_hits, cls_hits
+        self.words = torch.zeros(answer_hits.WORDS, dtype=torch.int64, device=device)
+        self.cls_words = torch.zeros((self._MAX_CLS, cls_hits.WORDS), dtype=torch.int64, device=device)
+        self.keep_topk = bool(topk)
+        self._topk = None
+
+    def _ranked(self, data_dict: dict, types=None, n_types: int = 0) -> int:
+        """The gps_answer_hits launch of a batch -> B."""
+        from .common import answer_hits
+        scores, label = data_dict["answer_scores"], data_dict["answer_label"]
+        _need_gpu(type(self).__name__, self.words, scores, label)
+        B = int(scores.shape[0])
+        if self.keep_topk and (self._topk is None or self._topk.shape[0] != B):
+            self._topk = torch.full((B, self.K), -1, dtype=torch.int32, device=self.words.device)
+        answer_hits.hits(scores.detach(), label, self.words, k=self.K, types=types, n_types=n_types,
+                         topk=self._topk if self.keep_topk else None)
+        return B
+
+    def last_topk(self):
+        """(B, 10) int32 on the device: the last batch's ten best answer ids per question in rank order (-1 past the
+        vocabulary) -- with `og3d_logits.argmax` and `obj_boxes` what ScanQAEval's `save` branch writes per question
+        (evaluator/scanqa_eval.py:62-75).  Needs `topk=True`; None before the first update."""
+        if not self.keep_topk:
+            raise RuntimeError(f"{type(self).__name__} was built without topk=True")
+        return self._topk
+
+
+class ScanQACounter(_AnswerCounter):
+    """ScanQAEval.batch_metrics(include_count=True) with BaseEvaluator.update / record (evaluator/scanqa_eval.py:29-81,
+    evaluator/build.py:26-41) as integer pairs on the device.  One `update` is one gps_answer_hits launch (the ten best
+    answers of every question ranked by the law of include/gps_hip.h, ten label entries read per question), one
+    gps_cls_hits launch for the object-class keys and one gps_answer_fold launch -- no host sync, so it can be captured.
+
+    Keys: ans1_acc, ans10_acc (count: the questions), and `<key>_acc` for every 3-D `*logits` tensor whose leading shape
+    is `obj_labels`'s (hits among `obj_masks`, count `obj_masks.sum()`; scanqa_eval.py:48-54) -- none when the batch has
+    no `obj_labels`.  The key set of the first update holds until `reset()`.  `last()`: the last batch's ratios
+    hits / max(count, 1) as 0-dim float64 device tensors (clones, no sync); `result()` is the one read-back."""
+    _MAX_CLS = 8
+
+    def __init__(self, device: torch.device | str = "cuda", topk: bool = False):
+        super().__init__(device, topk)
+        n = 2 + self._MAX_CLS
+        self._sums = torch.zeros(2 * n, dtype=torch.int64, device=device)
+        self._last = torch.zeros(n, dtype=torch.float64, device=device)
+        self._keys = None
+
+    def reset(self) -> None:
+        for t in (self.words, self.cls_words, self._sums, self._last):
+            t.zero_()
+        self._keys = None
+
+    def update(self, data_dict: dict) -> None:
+        from .common import answer_hits, cls_hits
+        self._ranked(data_dict)
+        problems, keys = [], []
+        gt = data_dict.get("obj_labels")
+        if gt is not None:
+            for key, x in data_dict.items():
+                if key.endswith("logits") and torch.is_tensor(x) and x.dim() == 3 and x.shape[:2] == gt.shape:
+                    if len(keys) >= self._MAX_CLS:
+                        raise ValueError(f"ScanQACounter: more than {self._MAX_CLS} object logits tensors")
+                    problems.append(cls_hits.problem(x, gt, self.cls_words[len(keys)], sel=data_dict["obj_masks"]))
+                    keys.append(key.replace("logits", "acc"))
+        if self._keys is None:
+            self._keys = tuple(keys)
+        elif self._keys != tuple(keys):
+            raise ValueError(f"ScanQACounter: this batch gives the keys {keys}, the updates since the last reset gave "
+                             f"{list(self._keys)} (reset() the counter first)")
+        cls_hits.launch(problems, self.words.device)
+        answer_hits.fold_pairs(self.words, self.cls_words, len(keys), self._sums, self._last)
+
+    def _names(self):
+        return ["ans1_acc", "ans10_acc"] + list(self._keys or ())
+
+    def last(self) -> dict:
+        if self._keys is None:
+            return {}
+        vals = self._last.clone()
+        return {k: vals[i] for i, k in enumerate(self._names())}
+
+    def result(self, include_count: bool = False) -> dict:
+        """The reference's keys: (hits, count) pairs, or the ratios hits / max(count, 1)."""
+        if self._keys is None:
+            return {}
+        s = self._sums.tolist()
+        pairs = {k: (s[2 * i], s[2 * i + 1]) for i, k in enumerate(self._names())}
+        if include_count:
+            return pairs
+        return {k: h / max(n, 1) for k, (h, n) in pairs.items()}
+
+
+class SQA3DCounter(_AnswerCounter):
+    """SQA3DEval.batch_metrics / update / record / reset (evaluator/sqa3d_eval.py:49-137) with counts and float64
+    bookkeeping on the device: one gps_answer_hits launch (ranked ten best answers, question types 0..5), one
+    gps_cls_hits launch for obj_cls_raw_acc and one gps_answer_fold launch per `update` -- no host sync, so it can be
+    captured.  Keys: target_metric (= ans1_acc), obj_cls_raw_acc, ans1_acc, ans10_acc, type0_acc .. type5_acc; `last()`
+    adds the batch's type{t}_count (the reference's 1e-10 + 1 + 1 + ... chain).  `result()` is `record()`: the plain keys'
+    sum(ratio * B) / sum(B), the types' sum(acc_t * count_t) / (1e-10 + sum(count_t)).  A batch without a masked object,
+    or without `obj_cls_raw_logits`, gives obj_cls_raw_acc = 0 where the reference divides by zero / raises."""
+    N_TYPES = 6
+    KEYS = ("target_metric", "obj_cls_raw_acc", "ans1_acc", "ans10_acc") + tuple(f"type{t}_acc" for t in range(6))
+
+    def __init__(self, device: torch.device | str = "cuda", topk: bool = False):
+        super().__init__(device, topk)
+        n = self.N_TYPES
+        self._last = torch.zeros(4 + 2 * n, dtype=torch.float64, device=device)
+        self._acc = torch.zeros(4 + n, dtype=torch.float64, device=device)
+        self._type_total = torch.full((n,), 1e-10, dtype=torch.float64, device=device)
+        self._total = torch.zeros(1, dtype=torch.float64, device=device)
+        self._seen = False
+
+    def reset(self) -> None:
+        for t in (self.words, self.cls_words, self._last, self._acc, self._total):
+            t.zero_()
+        self._type_total.fill_(1e-10)
+        self._seen = False
+
+    def update(self, data_dict: dict) -> None:
+        from .common import answer_hits, cls_hits
+        B = self._ranked(data_dict, types=data_dict["sqa_type"], n_types=self.N_TYPES)
+        raw = data_dict.get("obj_cls_raw_logits")
+        if raw is not None:
+            cls_hits.launch([cls_hits.problem(raw, data_dict["obj_labels"], self.cls_words[0],
+                                              sel=data_dict["obj_masks"])], self.words.device)
+        answer_hits.fold_sqa3d(self.words, self.cls_words if raw is not None else None, self.N_TYPES, float(B),
+                               self._last, self._acc, self._type_total, self._total)
+        self._seen = True
+
+    def last(self) -> dict:
+        if not self._seen:
+            return {}
+        vals = self._last.clone()
+        names = list(self.KEYS) + [f"type{t}_count" for t in range(self.N_TYPES)]
+        return {k: vals[i] for i, k in enumerate(names)}
+
+    def result(self) -> dict:
+        if not self._seen:
+            return {}
+        vals = torch.cat([self._acc, self._type_total, self._total]).tolist()
+        n, total = self.N_TYPES, vals[-1]
+        out = {k: vals[i] / total for i, k in enumerate(self.KEYS[:4])}
+        out.update({f"type{t}_acc": vals[4 + t] / vals[4 + n + t] for t in range(n)})
+        return out
 
 
 def dp_self_check(make_engine, batches, rtol_loss: float = 2e-3, rtol_grad: float = 3e-2) -> dict:
