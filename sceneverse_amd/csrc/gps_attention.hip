@@ -724,7 +724,8 @@ __global__ __launch_bounds__(512) void attn_bwd_kernel(const Params P) {
 //             across the four lane groups at the end), pass B streams them again, recomputes the logits, and feeds
 //             P V chunk by chunk;
 //   backward  delta = rowsum(dO * O) is computed first (needs the forward output), so the dQ pass can treat every
-//             32-key chunk independently; the dK / dV pass is the chunked loop of the recompute kernel.
+//             32-key chunk independently; the dK / dV pass is the chunked loop of the recompute kernel.  The plain form
+//             with dropout replaces it per query strip by rowsum(P' dP') (one more sweep of the keys; see there).
 // K and V stay ROW-major in LDS and serve both operand kinds: A fragments by 16-byte reads, B fragments by the
 // hardware-transposed ds_read_b64_tr_b16 (no transposing stores, no V^T / K^T tiles).
 // ==========================================================================================
@@ -951,8 +952,36 @@ __global__ __launch_bounds__(1024) void attn_bwd_stream_kernel(const Params P) {
       dw[d] = 0.f;
     }
     const float lse_q = lse_s[qi < rows_q ? qi : 0];
-    const float delta = delta_s[qi < rows_q ? qi : 0];
+    float delta = delta_s[qi < rows_q ? qi : 0];
     const unsigned int rp = (bh_base + qi) * pitch2;
+    if (!SPATIAL && dropout) {
+      // With dropout the forward output is bf16(sum P' v): a row that one kept key dominates has dP' == delta in exact
+      // arithmetic (dS = 0), and rowsum(dO * O) leaves dO . (O - bf16(O)) there instead -- noise in dQ / dK of 1e-2 of a
+      // full row's gradient where the truth is zero.  So the plain form takes delta = rowsum(P' dP') from the
+      // probabilities themselves, as the register-resident kernels do: one more sweep of S and dO V^T over the keys.
+      float dsum = 0.f;
+      for (int j = 0; j < nt; ++j) {
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f}, dacc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int cc = 0; cc < 2; ++cc) {
+          const u32x4 a = *reinterpret_cast<const u32x4 *>(Ks + (16 * j + m) * KS + 32 * cc + 8 * g);
+          const u32x4 av = *reinterpret_cast<const u32x4 *>(Vs + (16 * j + m) * KS + 32 * cc + 8 * g);
+          acc = mfma32(as_frag(a), bq[cc], acc);
+          dacc = mfma32(as_frag(av), bdo[cc], dacc);
+        }
+        const int t0 = 16 * j + 4 * g;
+        const f32x4 kt = *reinterpret_cast<const f32x4 *>(mb + t0);
+        const unsigned int r01 = pair_rng(seedmix, rp, t0), r23 = pair_rng(seedmix, rp, t0 + 2);
+        const bool keep[4] = {(r01 & 0xFFFFu) >= thr16, (r01 >> 16) >= thr16, (r23 & 0xFFFFu) >= thr16, (r23 >> 16) >= thr16};
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float p = __builtin_amdgcn_exp2f(fmaf(acc[r], 0.125f * kLog2e, kt[r]) - lse_q);
+          dsum = fmaf(p, keep[r] ? dacc[r] : 0.f, dsum);
+        }
+      }
+      delta = xor_sum_g(dsum) * keep_scale;
+      if (g == 0) delta_s[qi] = delta;           // pass 2 reads it behind the barrier below; qi < 16 ntq <= rows_q
+    }
     f32x4 o[4];
 #pragma unroll
     for (int n = 0; n < 4; ++n) o[n] = f32x4{0.f, 0.f, 0.f, 0.f};

@@ -66,9 +66,12 @@ CASES = [(3, 80, True), (8, 80, True), (2, 130, False), (8, 130, False), (2, 37,
          (1, 145, True), (2, 177, False)]
 
 
-@pytest.fixture(params=["default", "resident", "streaming", "planes", "blocks", "kv-resident"])
+@pytest.fixture(params=["default", "resident", "streaming", "planes", "blocks", "kv-resident", "fused-bwd", "product"])
 def family(request):
-    """Which kernels serve a call.  The two PRODUCT defaults:
+    """Which kernels serve a call.  "product" is the plain form as the training step runs it (plain mode 13 = 1 | 4 | 8:
+    K / V-resident kernels up to 144 tokens, above that the block-streaming forward with the one-launch backward of
+    gps_attention_fa.hip up to 320 tokens and the whole-sequence backward beyond), "fused-bwd" (mode 9 = 1 | 8) that
+    forward and the one-launch backward at every length up to 320.  The two PRODUCT defaults:
       "planes"  the spatial form on gps_attention_sp.hip (fp16 planes of the pairwise tensor, bf16 conditioning vector
                 read in place; L <= 144),
       "blocks"  the plain form on the block-streaming kernels of gps_attention_fa.hip (any length; forward AND backward --
@@ -83,7 +86,7 @@ def family(request):
     lib = _native.load()
     lib.gps_attn_set_stream_min_tiles(*{"resident": (10, 10), "streaming": (1, 1)}.get(request.param, (1, 10)))
     FA.set_spatial_planes(request.param == "planes")
-    FA.set_plain_mode({"blocks": 3, "kv-resident": 4}.get(request.param, 0))
+    FA.set_plain_mode({"blocks": 3, "kv-resident": 4, "fused-bwd": 9, "product": 13}.get(request.param, 0))
     yield request.param
     lib.gps_attn_set_stream_min_tiles(1, 10)
     FA.set_spatial_planes(True)
@@ -95,8 +98,8 @@ def _skip_duplicates(family, L, spatial):
         pytest.skip("rows above 144 tokens stream in every setting of the general kernels")
     if family == "planes" and (not spatial or L > 144):
         pytest.skip("the plane form is the spatial term's, up to 144 tokens")
-    if family == "blocks" and spatial:
-        pytest.skip("the block-streaming kernels serve the plain form")
+    if family in ("blocks", "fused-bwd", "product") and spatial:
+        pytest.skip("the block-streaming kernels, the one-launch backward and the plain mode serve the plain form")
     if family == "kv-resident" and (spatial or L > 144):
         pytest.skip("the K / V-resident plain kernels serve fixed-length rows up to 144 tokens")
 
@@ -152,7 +155,7 @@ def test_streaming_and_resident_kernels_agree_at_the_switch():
 
 @pytest.mark.parametrize("L", [80, 200, 300])
 def test_dropout_is_reproducible_linear_and_adjoint(L, family):
-    if family in ("planes", "blocks", "kv-resident"):
+    if family in ("planes", "blocks", "kv-resident", "fused-bwd", "product"):
         pytest.skip("this test drives the SPATIAL form with dropout: served by the general kernels (other families)")
     _skip_duplicates(family, L, True)
     B = 2
