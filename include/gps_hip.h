@@ -888,6 +888,83 @@ GPS_API int gps_obj_select_pred(int B, int O, int M, int n_objects, int n_labels
                                 int32_t *n_rem, uint8_t *is_multiple, uint8_t *is_hard, int64_t *iou25,
                                 int64_t *iou50, int64_t *tgt_id, int64_t *obj_labels, gps_stream_t stream);
 
+/* ---- a ScanQA / SQA3D batch from one question id per row: targets, crop, answer labels ------------------------
+ * Replaces, per batch and in ONE launch (no atomics, no workspace, no scratch, no host sync; capturable), the object
+ * selection and the target tensors of ScanNetScanQAOld.__getitem__ (data/datasets/scannet_old.py:326-484) and
+ * ScanNetSQA3D.__getitem__ (scannet_old.py:94-232): the filter (:373-392), the target lists of 'gt' and of 'pred' by
+ * IoU >= 0.25 (:394-422), the crop (:425-443), the pad slot of a question without a target (:446-448), the three
+ * multi-hots (:453-467) and SQA3D's random.choice of a situation (:105-112).  row_obj is the table of
+ * gps_obj_processing_post, sent_idx a text id of gps_text_batch.
+ *
+ * The resident questions (gps_qa_questions, all arrays on the device, int32):
+ *   ann_range (nq, 2) [first, last) global ids of the question's scan's ANNOTATED objects; prop_range (nq, 2) those of
+ *   its proposals ('pred' only); both clamped to [0, n_objects].  tgt_first (nq + 1) CSR into tgt_id / tgt_label (n_tgt):
+ *   the question's target list T, GLOBAL ids of annotated objects, and per entry the label it stands for (the object's
+ *   own, or the reference's cat2int[object_name]).  ans_first (nq + 1) CSR into ans_id (n_ans): answer ids in the caller's
+ *   vocabulary.  sqa_type (nq).  var_first (nq + 1) CSR into var_text (n_var): the text ids of the question's variants
+ *   (situation_i + question; ScanQA has one); variant v of the whole table is entry v of var_text.  Every CSR bound is
+ *   clamped to its array; of a list of more than GPS_QA_MAX_TGT targets the first GPS_QA_MAX_TGT are read.
+ * Inputs: q_idx (B) int32, the row's question; labels, match_labels (n_objects) int32 and boxes (n_objects, 6) float64 as
+ *   in gps_obj_select_pred; keep: u8, keep_rows == 0: one (n_labels) table, keep_rows > 0: (keep_rows, n_labels), the row
+ *   of the question's CHOSEN variant (filter_lang: `int2cat[l] in sentence`; a variant at or past keep_rows keeps
+ *   nothing); not read in 'pred' mode.  flags: GPS_QA_PRED ('pred': rows of proposals), GPS_QA_MATCHED (class comparisons
+ *   read match_labels: ScanQA relabels its proposals, :357-371; SQA3D does not), GPS_QA_TRAIN (the variant is drawn),
+ *   GPS_QA_INT64 (the three multi-hots are int64 0 / 1, SQA3D's .long(); else float32, ScanQA's .float()).
+ *   M = the number of objects a row may hold (the loaders' max_obj_len - 1), M <= O <= GPS_REFER_MAX_OBJ.
+ * Outputs, every element written: row_obj (B, O) int32 global ids, -1 past the row; n_sel, n_rem, n_tgt (B) int32;
+ *   sent_idx (B) int32; sqa_type (B) int64; obj_labels (B, O) int64, the class c_p of the object in each slot (the
+ *   loaders' obj_labels), -100 past the row; tgt_object_id (B, O), tgt_object_label (B, n_labels), answer_label (B, A).
+ * Per row b, q = q_idx[b]; T counts a repeated id once, at its first place (label included); k = len(T).
+ *   Variant: pick[b] when pick is given (a replay of random.choice), else rng_u32(S + 4, b) % n_variants with
+ *     GPS_QA_TRAIN and 0 without; a pick outside [0, n_variants) counts as 0.  v = var_first[q] + pick,
+ *     sent_idx = var_text[v] (-1 for a question without a variant).  Streams of S = seed + (seed_dev ? *seed_dev : 0):
+ *     S, S + 1, S + 2 gps_text_batch, S + 3 the fill of all three selections, S + 4 this pick.
+ *   'gt': positions p of the annotated range, l_p = labels[first + p], kept_p = 0 <= l_p < n_labels && keep[..][l_p].
+ *     sel = the kept positions ascending, then every target that is not kept, in list order.
+ *   'pred': sel = all positions of the proposal range, ascending.  The target list becomes the positions whose box
+ *     overlaps the box of any entry of T at IoU >= 0.25 (the float64 expression of gps_refer_targets), ASCENDING; each
+ *     carries the label of the FIRST entry of T it overlaps; k = their number.
+ *   Class of a position: c_p = match_labels[g_p] with GPS_QA_MATCHED, else labels[g_p]; compared as integers.
+ *   n = len(sel).  n <= M: the row is sel; the targets' slots are their indices in it.
+ *   n > M: the first min(k, M) targets, in list order ('gt') or ascending ('pred'), in slots 0, 1, ..; then the
+ *     non-target entries of sel whose class is the label of a target, in sel order, the row cut at M; if it is still
+ *     shorter than M, remained = the other non-targets of sel in sel order and the row is completed with
+ *     remained[order[0]], remained[order[1]], ... -- replay form and device law exactly those of gps_obj_select: stream
+ *     S + 3, key (uint64(rng_u32(S + 3, b * 2^20 + r)) << 32) | r.  With k == 0 every entry of sel is in remained.
+ *   n_sel = the row's length; n_rem = len(remained) when the fill ran, else 0; n_tgt = min(k, M).
+ *   tgt_object_id: 1 at the slots of the row's targets; with k == 0 the single 1 at slot n_sel (when n_sel < O: the
+ *     reference's vector has n + 1 entries, ScanFamilyDatasetWrapperOld pads it to max_obj_len = M + 1) and label 5 set in
+ *     tgt_object_label (:446-448).  tgt_object_label: 1 at the labels of the row's targets; answer_label: 1 at the
+ *     question's answer ids.  An id outside [0, n_labels) / [0, A) sets nothing.
+ *   sqa_type[b] = sqa_type[q].
+ * Four definitions of this library, where the reference has none:
+ *   unkept targets.  The reference appends a target that the filter dropped only under filter_lang (:379-381); without
+ *     it `selected_obj_idxs.index` fails (:396).  Here it is appended in both modes.
+ *   repeated targets.  The reference would put the object into the row twice; here a repeated id counts once.
+ *   k > M.  The reference overshoots max_obj_len and fails its assertion (:443); here the row is the first M targets.
+ *   EMPTY rows (row -1, obj_labels -100, n_sel = n_rem = n_tgt = 0, the three multi-hots all 0, sent_idx -1, sqa_type 0): q outside
+ *     [0, nq); a scan (its proposals in 'pred' mode) of more than GPS_OBJ_SELECT_MAX_SCAN positions; a target outside its
+ *     scan's annotated range.  No id read from device memory becomes an address unchecked.
+ * GPS_ERR_INVALID_ARGUMENT: a negative size, M < 1, M > O, order given with R < M, an unknown flag, a NULL mandatory
+ *   pointer (B > 0).  GPS_ERR_UNSUPPORTED: O > GPS_REFER_MAX_OBJ.  B == 0: GPS_OK, nothing launched. */
+#define GPS_QA_MAX_TGT 32
+#define GPS_QA_PRED 1
+#define GPS_QA_MATCHED 2
+#define GPS_QA_TRAIN 4
+#define GPS_QA_INT64 8
+typedef struct gps_qa_questions {
+  int nq, n_tgt, n_ans, n_var;
+  const int32_t *ann_range, *prop_range, *tgt_first, *tgt_id, *tgt_label, *ans_first, *ans_id, *sqa_type, *var_first,
+      *var_text;
+} gps_qa_questions;
+GPS_API int gps_obj_select_qa(int B, int O, int M, int A, int n_objects, int n_labels, int flags,
+                              const gps_qa_questions *questions, const int32_t *q_idx, const double *boxes,
+                              const int32_t *labels, const int32_t *match_labels, const uint8_t *keep, int keep_rows,
+                              const int32_t *order, int R, const int32_t *pick, uint64_t seed,
+                              const uint64_t *seed_dev, int32_t *row_obj, int32_t *n_sel, int32_t *n_rem,
+                              int32_t *n_tgt, int32_t *sent_idx, int64_t *sqa_type, int64_t *obj_labels,
+                              void *tgt_object_id, void *tgt_object_label, void *answer_label, gps_stream_t stream);
+
 /* ---- accuracy counters of the pre-train, ReferIt3D and object-class evaluators -------------------------
  * Replaces the arg-max / compare / sum / `.item()` chains of PretrainEval.batch_metrics (evaluator/pretrain_eval.py:21-67),
  * ReferIt3DEval.batch_metrics (evaluator/referit3d_eval.py:14-83) and PretrainObjEval.batch_metrics

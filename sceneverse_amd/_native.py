@@ -89,7 +89,15 @@ class AnswerHitsArgs(ctypes.Structure):
                 ("k", _i), ("rows_dev", _vp), ("topk", _vp), ("words", _vp)]
 
 
+class QAQuestions(ctypes.Structure):
+    """struct gps_qa_questions of include/gps_hip.h, field for field."""
+    _fields_ = [("nq", _i), ("n_tgt", _i), ("n_ans", _i), ("n_var", _i), ("ann_range", _vp), ("prop_range", _vp),
+                ("tgt_first", _vp), ("tgt_id", _vp), ("tgt_label", _vp), ("ans_first", _vp), ("ans_id", _vp),
+                ("sqa_type", _vp), ("var_first", _vp), ("var_text", _vp)]
+
+
 CLS_HITS_MAX_PROBLEMS, CLS_HITS_WAVE_MAX_COLS, METRICS_MAX_TERMS = 8, 1024, 16
+QA_MAX_TGT, QA_PRED, QA_MATCHED, QA_TRAIN, QA_INT64 = 32, 1, 2, 4, 8
 ANSWER_MAX_K, ANSWER_MAX_TYPES, ANSWER_WORDS, ANSWER_WAVE_MAX_COLS, ANSWER_FOLD_MAX_CLS = 16, 8, 19, 64, 8
 ATTN_BF16, ATTN_F32 = 0, 1
 ATTN_COMPUTE_NATIVE, ATTN_COMPUTE_FP8 = 0, 1
@@ -161,6 +169,8 @@ SIGNATURES = {
     "gps_obj_select": [_i] * 6 + [_vp] * 4 + [_i, _vp, _vp, _i, ctypes.c_ulonglong] + [_vp] * 8,
     "gps_proposal_labels": [_i, _i] + [_vp] * 6,
     "gps_obj_select_pred": [_i] * 5 + [_vp] * 9 + [_i, ctypes.c_ulonglong] + [_vp] * 12,
+    "gps_obj_select_qa": [_i] * 7 + [ctypes.POINTER(QAQuestions)] + [_vp] * 5 + [_i, _vp, _i, _vp, ctypes.c_ulonglong]
+                         + [_vp] * 12,
     "gps_cls_hits": [ctypes.POINTER(ClsHitsProblem), _i, _vp],
     "gps_metrics_fold": [_i, ctypes.POINTER(MetricTerm), ctypes.c_double, _i, _vp, _vp, _vp, _vp],
     "gps_answer_hits": [ctypes.POINTER(AnswerHitsArgs), _vp],

@@ -31,6 +31,7 @@ SOURCES = [
     ("gps_text.hip", []),
     ("gps_obj_select.hip", []),
     ("gps_obj_select_pred.hip", ["-ffp-contract=off"]),
+    ("gps_obj_select_qa.hip", ["-ffp-contract=off"]),
     ("gps_reduce.hip", []),
     ("gps_embedding.hip", []),
     ("gps_bert_embed.hip", []),

@@ -136,6 +136,26 @@ def synth_packed_texts(n_sent: int, n_cap: int, seed: int = 42, device: str | to
     return texts.finalize()
 
 
+def synth_packed_questions(packed, scan_ids, n_questions: int, n_texts: int, seed: int = 42, n_answers: int = 8864,
+                           max_variants: int = 3, max_targets: int = 3):
+    """Questions for `data.gpu_qa` about the finalized scans `scan_ids` of `packed`: question i is about a scan drawn
+    uniformly, has 0 .. max_targets distinct targets among that scan's annotated objects, 0 - 3 answer ids below
+    n_answers, an sqa_type in 0..5 and 1 .. max_variants text ids below n_texts (ids of a `synth_packed_texts` corpus).
+    -> the finalized PackedQuestions on the scans' device."""
+    from .gpu_qa import PackedQuestions
+    rng = np.random.default_rng(seed + 104729)
+    questions = PackedQuestions(packed.device)
+    for _ in range(n_questions):
+        sid = scan_ids[int(rng.integers(len(scan_ids)))]
+        n_obj = len(packed.scan_objects(sid))
+        k = int(rng.integers(0, min(max_targets, n_obj) + 1))
+        questions.add_question(sid, targets=rng.choice(n_obj, size=k, replace=False) if k else (),
+                               answers=rng.choice(n_answers, size=int(rng.integers(0, min(3, n_answers) + 1)), replace=False),
+                               texts=rng.integers(0, n_texts, size=int(rng.integers(1, max_variants + 1))),
+                               sqa_type=int(rng.integers(0, 6)))
+    return questions.finalize(packed)
+
+
 def adversarial_objects(n_pts: int = 1024, seed: int = 7) -> torch.Tensor:
     """(6, n_pts, 3) xyz clouds that stress the bit-exactness rules of SURVEY.md App. B:
     0 heavy duplicates (FPS ties), 1 many points inside |p|^2 <= 1e-3 (FPS skip rule),
