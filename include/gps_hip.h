@@ -683,6 +683,101 @@ GPS_API int gps_obj_processing_aug(int n_rows, int n_points, const float *xyz, c
                                    float *obj_fts, float *obj_locs, float *obj_boxes, uint8_t *obj_masks,
                                    gps_stream_t stream);
 
+/* ---- the two object launches with a seed word ------------------------------------------------------------
+ * gps_obj_processing_post / _aug with one more argument: seed_dev, one uint64 word on the device or NULL.  The seed of
+ * the launch is S = seed + (seed_dev ? *seed_dev : 0) with unsigned wrap (effective_seed of csrc/gps_dropout.h), read on
+ * the device, so a captured launch redraws its samples and its jitter noise when the word is advanced between replays.
+ * Everything behind S is the by-value entry: key = mix64(S ^ mix64(row)), the same sampler, the same noise stream.
+ * Bit for bit on every output: _sw(seed = s, *seed_dev = w) equals the by-value entry with seed = s + w, and
+ * _sw(seed_dev = NULL) equals the by-value entry.  Arguments, checks and statuses are those of the by-value entries. */
+GPS_API int gps_obj_processing_post_sw(int n_rows, int n_points, const float *xyz, const void *rgb, int rgb_is_u8,
+                                       const int64_t *obj_offsets, const int32_t *row_obj,
+                                       const int32_t *sample_idx, uint64_t seed, const uint64_t *seed_dev,
+                                       const float *rot, const int32_t *row_rot, float *obj_fts, float *obj_locs,
+                                       float *obj_boxes, uint8_t *obj_masks, gps_stream_t stream);
+GPS_API int gps_obj_processing_aug_sw(int n_rows, int n_points, const float *xyz, const void *rgb, int rgb_is_u8,
+                                      const int64_t *obj_offsets, const int32_t *row_obj,
+                                      const int32_t *sample_idx, const void *jitter_noise, int noise_is_f64,
+                                      uint64_t seed, const uint64_t *seed_dev, const double *aug,
+                                      const int32_t *row_aug, int n_aug, float *obj_fts, float *obj_locs,
+                                      float *obj_boxes, uint8_t *obj_masks, gps_stream_t stream);
+
+/* ---- the draws of DataAugmentor and of build_rotate_mat: the parameter table in one launch ------------------
+ * Replaces, per batch and in ONE launch (no atomics, no workspace, no host sync; capturable), the draws of
+ * DataAugmentor.scene_aug / obj_aug (data/datasets/data_augmentor.py:39-154) and, in its second mode, build_rotate_mat
+ * (data/data_utils.py:163-178, rand_angle 'axis').  The augmentation arithmetic is gps_obj_processing_aug's; this entry
+ * only writes the table it reads.  On a split other than 'train' the caller launches nothing and passes aug = NULL.
+ *
+ * gps_aug_draw_args: mode; B scenes of O object slots; scene_on / obj_on: `aug_list` names scene_aug / obj_aug; per knob
+ *   (gps_aug_knob) enabled (check_key), p (1.0 when the config gives none: check_p always fires then), value[], axis_align,
+ *   shuffle.  scene_scale reads value[0], value[1] (low, high); scene_flip reads no value.  color_jitter: on / off;
+ *   jitter_on + jitter_value[3]: obj_aug.random_jitter enabled and its scale (a scalar thrice).  As in the reference,
+ *   random_jitter.p and accord_to_size are not read, and order_shuffle / pts_shuffle are not drawn (a permutation of the
+ *   sample commutes with everything downstream; device-drawn samples are in random order).  seed, seed_dev:
+ *   S = seed + (seed_dev ? *seed_dev : 0).
+ *
+ * mode GPS_AUG_DRAW_TABLE writes aug (n_aug, GPS_OBJ_AUG_STRIDE) float64 and row_aug (B * O) int32, every element:
+ *   per_obj = obj_on && (obj_trans.enabled || obj_rot.enabled).  n_aug = B, entry b, without per_obj (the published
+ *   configs: one of four z-rotations per scene); n_aug = B * O, entry b * O + o, with it -- fixed by the config, never by
+ *   the draws.  row_aug[b * O + o] = the entry, or -1 when its flags are 0 (nothing fired); such an entry is all zeros.
+ *   The law.  Stream S + 6 of csrc/gps_dropout.h (S .. S + 2 gps_text_batch, S + 3 the fills, S + 4 the QA pick, S + 5 the
+ *   caption choice of gps_item_rows, S + 7 the rotation mode below).  Draw k of slot s of scene b is the word
+ *   u(k) = rng_u32(S + 6, (b * (O + 1) + s) * 64 + k), s = 0 for the scene and 1 + o for object slot o: every draw has
+ *   its own counter, so none depends on whether an earlier knob fired.  k, for scene and object slots alike:
+ *     GPS_AUG_K_TRANS_P 0      translation fires        GPS_AUG_K_TRANS 1 .. 6     its normals x, y, z (two words each)
+ *     GPS_AUG_K_SCALE_P 7      scaling fires            GPS_AUG_K_SCALE 8          its uniform
+ *     GPS_AUG_K_FLIP_P 9       flip fires               GPS_AUG_K_FLIP 10          flip_type
+ *     GPS_AUG_K_ROT_P 11       rotation fires           GPS_AUG_K_ROT_ANGLE 12 .. 14  angles x, y, z
+ *     GPS_AUG_K_ROT_PERM 15    the order of rx, ry, rz  GPS_AUG_K_RGB 16 .. 21     colour delta r, g, b (two words each)
+ *   A knob fires iff it is enabled and u < T(p), T(p) = floor(p * 2^32) as a 64-bit number (gps_text_batch's T).
+ *   Integer choice among n: (uint64(u) * n) >> 32.  Uniform: u * 2^-32.  Normal at k: u1 = (u(k) + 1) * 2^-32,
+ *   u2 = u(k + 1) * 2^-32, z = sqrt(-2 log u1) * cospi(2 u2) (the Box-Muller of the jitter noise).  All float64, no
+ *   contraction, in the order written:
+ *     translation[i] = z_i * value[i].  scale = uniform * (value[1] - value[0]) + value[0].
+ *     flip: flip_type = choice of 4; diag(-1, 1, 1), diag(1, -1, 1), diag(-1, -1, 1), identity.
+ *     colour delta[i] = z_i * 0.1.  jitter scale = jitter_value (no draw).
+ *     rotation: axis_align: a_i = choice of 4; value[i] == 0 -> cos 1, sin 0; value[i] == 1 -> the float64 values
+ *       math.cos / math.sin return for 0, pi/2, pi, pi*3/2 (6.123233995736766e-17, not 0: the reference keeps it), from a
+ *       constant table; otherwise theta_i = angle[a_i] * value[i] through cos / sin.  Free angles: theta_i = ((uniform *
+ *       2) * pi - pi) * value[i] through cos / sin.  rx = [1 0 0; 0 c -s; 0 s c], ry = [c 0 s; 0 1 0; -s 0 c],
+ *       rz = [c s 0; -s c 0; 0 0 1] (data_augmentor.py:78-89; rz is the transpose of build_rotate_mat's).  shuffle: the
+ *       three are taken in the order of permutation number (choice of 6) of (0, 1, 2) in lexicographic order, else
+ *       rx, ry, rz.  The matrix is (m0 . m1) . m2, every element ((a0 * b0 + a1 * b1) + a2 * b2).
+ *   Where the reference's numbers are integers (flags, flip, the axis-aligned table, the jitter scale) and for the scale
+ *   the table is a function of the words alone; the free angles, translations and colour deltas pass through the
+ *   device's sin / cos / log / sqrt / cospi.
+ * mode GPS_AUG_DRAW_ROT writes rot (B, 3, 3) float32 and row_rot (B * O) int32: a = (uint64(rng_u32(S + 7, b)) * 4) >> 32;
+ *   row_rot[b * O + o] = -1 for a == 0 (build_rotate_mat returns None), else b; rot[b] = [c -s 0; s c 0; 0 0 1] with
+ *   c, s the table's float64 values rounded to float32 (data_utils.py:171-175), the identity for a == 0.
+ * GPS_ERR_INVALID_ARGUMENT: args NULL, a negative size, an unknown mode, a p outside [0, 1], a NULL output of the mode
+ * (B * O > 0).  B * O * GPS_OBJ_AUG_STRIDE above 2^31 - 1: GPS_ERR_UNSUPPORTED.  B * O == 0: GPS_OK, nothing launched. */
+#define GPS_AUG_DRAW_TABLE 0
+#define GPS_AUG_DRAW_ROT 1
+#define GPS_AUG_K_TRANS_P 0
+#define GPS_AUG_K_TRANS 1
+#define GPS_AUG_K_SCALE_P 7
+#define GPS_AUG_K_SCALE 8
+#define GPS_AUG_K_FLIP_P 9
+#define GPS_AUG_K_FLIP 10
+#define GPS_AUG_K_ROT_P 11
+#define GPS_AUG_K_ROT_ANGLE 12
+#define GPS_AUG_K_ROT_PERM 15
+#define GPS_AUG_K_RGB 16
+typedef struct gps_aug_knob {
+  int enabled, axis_align, shuffle, reserved;
+  double p;
+  double value[3];
+} gps_aug_knob;
+typedef struct gps_aug_draw_args {
+  int mode, B, O, scene_on, obj_on, color_jitter, jitter_on, reserved;
+  gps_aug_knob scene_trans, scene_scale, scene_flip, scene_rot, obj_trans, obj_rot;
+  double jitter_value[3];
+  uint64_t seed;
+  const uint64_t *seed_dev;
+} gps_aug_draw_args;
+GPS_API int gps_aug_draw(const gps_aug_draw_args *args, double *aug, int32_t *row_aug, float *rot, int32_t *row_rot,
+                         gps_stream_t stream);
+
 /* ---- ScanRefer targets for predicted proposals: boxes, IoU flags, metrics ------------------------------
  * Replaces, for a `pc_type: 'pred'` (and 'gt') ScanRefer batch, what ScanBase._load_scan / _getitem_refer derive
  * from 3-D box IoU on the loader workers (data/datasets/base.py:105-141, :348-417, :453-454, :478-483), the padding
@@ -964,6 +1059,38 @@ GPS_API int gps_obj_select_qa(int B, int O, int M, int A, int n_objects, int n_l
                               const uint64_t *seed_dev, int32_t *row_obj, int32_t *n_sel, int32_t *n_rem,
                               int32_t *n_tgt, int32_t *sent_idx, int64_t *sqa_type, int64_t *obj_labels,
                               void *tgt_object_id, void *tgt_object_label, void *answer_label, gps_stream_t stream);
+
+/* ---- a pre-train / grounding row's facts from one item id ------------------------------------------------------
+ * Replaces, per batch and in ONE launch (no atomics, no workspace, no host sync; capturable), the per-sample look-ups of
+ * ScanBase._getitem_refer / _getitem_finalrefer (data/datasets/base.py:348-417, :851-957): the item's scan, the position
+ * of its target among the scan's annotated objects, cat2int[instance_type], its sentence, and np.random.choice of one
+ * of the scan's captions (base.py:851-856).  Its outputs are the scan_range / prop_range / tgt_obj / tgt_label of
+ * gps_obj_select and gps_obj_select_pred (tgt_obj there is global: position + scan_range[b][0]) and the sent_idx / cap_idx
+ * of gps_text_batch.
+ *
+ * The resident items (gps_item_table, all arrays on the device, int32): per item its scan's index item_scan, the
+ *   target's position item_tgt, item_label and the sentence's text id item_sent (n_items each); per scan scan_range and
+ *   prop_range (n_scans, 2) [first, last) global ids of its annotated objects and of its proposals ((0, 0) without
+ *   proposals), and cap_first (n_scans + 1) CSR into cap_text (n_caps), the text ids of its captions, every bound
+ *   clamped to the array; default_caption: the text id of a scan without captions.
+ * Per row b, i = item_ids[b], s = item_scan[i]: scan_range[b], prop_range[b] = the scan's; tgt_obj[b] = item_tgt[i];
+ *   tgt_label[b] = item_label[i]; sent_idx[b] = item_sent[i]; scan_idx[b] = s.
+ *   Caption: n = the scan's number of captions; n == 0 -> default_caption; else p = pick[b] when pick is given (a replay
+ *   of np.random.choice(len(scene_caps)); a pick outside [0, n) counts as 0), else rng_u32(S + 5, b) % n with
+ *   S = seed + (seed_dev ? *seed_dev : 0) (the form of the QA variant pick; stream S + 5); cap_idx[b] = the p-th.
+ *   UNDEFINED rows, where the reference fails with a KeyError: i outside [0, n_items), or s outside [0, n_scans): both
+ *   ranges (0, 0), tgt_obj = tgt_label = 0, sent_idx = cap_idx = scan_idx = -1 -- with these gps_obj_select / _pred give
+ *   an EMPTY row and gps_text_batch an empty text.  No id read from device memory becomes an address unchecked.
+ * GPS_ERR_INVALID_ARGUMENT: a negative size, items NULL, a NULL table array of non-zero length, cap_first NULL, a NULL
+ *   mandatory pointer (B > 0; pick and seed_dev are optional).  B == 0: GPS_OK, nothing launched. */
+typedef struct gps_item_table {
+  int n_items, n_scans, n_caps, default_caption;
+  const int32_t *item_scan, *item_tgt, *item_label, *item_sent, *scan_range, *prop_range, *cap_first, *cap_text;
+} gps_item_table;
+GPS_API int gps_item_rows(int B, const gps_item_table *items, const int32_t *item_ids, const int32_t *pick,
+                          uint64_t seed, const uint64_t *seed_dev, int32_t *scan_range, int32_t *prop_range,
+                          int32_t *tgt_obj, int32_t *tgt_label, int32_t *sent_idx, int32_t *cap_idx,
+                          int32_t *scan_idx, gps_stream_t stream);
 
 /* ---- accuracy counters of the pre-train, ReferIt3D and object-class evaluators -------------------------
  * Replaces the arg-max / compare / sum / `.item()` chains of PretrainEval.batch_metrics (evaluator/pretrain_eval.py:21-67),

@@ -96,9 +96,32 @@ class QAQuestions(ctypes.Structure):
                 ("sqa_type", _vp), ("var_first", _vp), ("var_text", _vp)]
 
 
+class AugKnob(ctypes.Structure):
+    """struct gps_aug_knob of include/gps_hip.h, field for field."""
+    _fields_ = [("enabled", _i), ("axis_align", _i), ("shuffle", _i), ("reserved", _i), ("p", ctypes.c_double),
+                ("value", ctypes.c_double * 3)]
+
+
+class AugDrawArgs(ctypes.Structure):
+    """struct gps_aug_draw_args of include/gps_hip.h, field for field."""
+    _fields_ = [("mode", _i), ("B", _i), ("O", _i), ("scene_on", _i), ("obj_on", _i), ("color_jitter", _i),
+                ("jitter_on", _i), ("reserved", _i),
+                ("scene_trans", AugKnob), ("scene_scale", AugKnob), ("scene_flip", AugKnob), ("scene_rot", AugKnob),
+                ("obj_trans", AugKnob), ("obj_rot", AugKnob), ("jitter_value", ctypes.c_double * 3),
+                ("seed", ctypes.c_ulonglong), ("seed_dev", _vp)]
+
+
+class ItemTable(ctypes.Structure):
+    """struct gps_item_table of include/gps_hip.h, field for field."""
+    _fields_ = [("n_items", _i), ("n_scans", _i), ("n_caps", _i), ("default_caption", _i), ("item_scan", _vp),
+                ("item_tgt", _vp), ("item_label", _vp), ("item_sent", _vp), ("scan_range", _vp), ("prop_range", _vp),
+                ("cap_first", _vp), ("cap_text", _vp)]
+
+
 CLS_HITS_MAX_PROBLEMS, CLS_HITS_WAVE_MAX_COLS, METRICS_MAX_TERMS = 8, 1024, 16
 QA_MAX_TGT, QA_PRED, QA_MATCHED, QA_TRAIN, QA_INT64 = 32, 1, 2, 4, 8
 ANSWER_MAX_K, ANSWER_MAX_TYPES, ANSWER_WORDS, ANSWER_WAVE_MAX_COLS, ANSWER_FOLD_MAX_CLS = 16, 8, 19, 64, 8
+AUG_DRAW_TABLE, AUG_DRAW_ROT = 0, 1
 ATTN_BF16, ATTN_F32 = 0, 1
 ATTN_COMPUTE_NATIVE, ATTN_COMPUTE_FP8 = 0, 1
 GEMM_NT, GEMM_NN, GEMM_TN = 0, 1, 2
@@ -161,6 +184,12 @@ SIGNATURES = {
                                 _vp, _vp],
     "gps_obj_processing_aug": [_i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, ctypes.c_ulonglong, _vp, _vp, _i,
                                _vp, _vp, _vp, _vp, _vp],
+    "gps_obj_processing_post_sw": [_i, _i, _vp, _vp, _i, _vp, _vp, _vp, ctypes.c_ulonglong, _vp, _vp, _vp, _vp, _vp, _vp,
+                                   _vp, _vp],
+    "gps_obj_processing_aug_sw": [_i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, ctypes.c_ulonglong, _vp, _vp, _vp, _i,
+                                  _vp, _vp, _vp, _vp, _vp],
+    "gps_aug_draw": [ctypes.POINTER(AugDrawArgs)] + [_vp] * 5,
+    "gps_item_rows": [_i, ctypes.POINTER(ItemTable), _vp, _vp, ctypes.c_ulonglong] + [_vp] * 9,
     "gps_obj_boxes": [_i, ctypes.c_longlong, _i, _vp, _i, _vp, _vp, _vp, _vp],
     "gps_refer_targets": [_i, _i, _i, _i] + [_vp] * 10,
     "gps_refer_metrics": [_i, _i, _vp, ctypes.c_longlong, _i] + [_vp] * 6,

@@ -32,6 +32,8 @@ SOURCES = [
     ("gps_obj_select.hip", []),
     ("gps_obj_select_pred.hip", ["-ffp-contract=off"]),
     ("gps_obj_select_qa.hip", ["-ffp-contract=off"]),
+    ("gps_aug_draw.hip", ["-ffp-contract=off"]),
+    ("gps_item_rows.hip", []),
     ("gps_reduce.hip", []),
     ("gps_embedding.hip", []),
     ("gps_bert_embed.hip", []),

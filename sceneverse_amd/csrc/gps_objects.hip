@@ -35,6 +35,12 @@ __device__ __forceinline__ uint64_t mix64(uint64_t z) {          // splitmix64 f
   return z ^ (z >> 31);
 }
 
+// The seed of a launch: `seed` plus the optional device word, read here so that a captured launch redraws when the word
+// is advanced between replays (effective_seed of gps_dropout.h: unsigned wrap).
+__device__ __forceinline__ uint64_t row_seed(uint64_t seed, const uint64_t *seed_dev) {
+  return seed + (seed_dev ? *seed_dev : 0ull);
+}
+
 // Device sampler.  k < num_points: WITH replacement (np.random.choice(..., replace=True) semantics):
 // an independent uniform index per draw.  k >= num_points: WITHOUT replacement: the first num_points
 // images of a keyed pseudo-random PERMUTATION of [0, k) -- a 4-round Feistel network on the smallest
@@ -94,7 +100,8 @@ __global__ __launch_bounds__(kBlock) void obj_processing_post_kernel(
     int n_points, const float *__restrict__ xyz, const uint8_t *__restrict__ rgb_u8,
     const float *__restrict__ rgb_f32, const int64_t *__restrict__ obj_offsets,
     const int32_t *__restrict__ row_obj, const int32_t *__restrict__ sample_idx, uint64_t seed,
-    const float *__restrict__ rot, const int32_t *__restrict__ row_rot, float *__restrict__ obj_fts,
+    const uint64_t *__restrict__ seed_dev, const float *__restrict__ rot, const int32_t *__restrict__ row_rot,
+    float *__restrict__ obj_fts,
     float *__restrict__ obj_locs, float *__restrict__ obj_boxes, uint8_t *__restrict__ obj_masks) {
   __shared__ double s_red[kWaves][9];
   __shared__ double s_out[9];
@@ -179,7 +186,7 @@ __global__ __launch_bounds__(kBlock) void obj_processing_post_kernel(
 
   // ---- pass 2: the sampled points, held in registers -----------------------------------------
   const bool replace = k < (uint32_t)n_points;
-  const uint64_t key = mix64(seed ^ mix64((uint64_t)row));   // per output row: a scene drawn twice differs
+  const uint64_t key = mix64(row_seed(seed, seed_dev) ^ mix64((uint64_t)row));   // per output row: a scene drawn twice differs
   double px[kMaxPer], py[kMaxPer], pz[kMaxPer];
   uint32_t src[kMaxPer];                         // sampled index, or (REC16) the record's colour word
   sx = sy = sz = 0;
@@ -261,11 +268,12 @@ __global__ __launch_bounds__(kBlock) void obj_processing_post_kernel(
 
 }  // namespace gps_obj
 
-extern "C" int gps_obj_processing_post(int n_rows, int n_points, const float *xyz, const void *rgb, int rgb_is_u8,
-                                       const int64_t *obj_offsets, const int32_t *row_obj,
-                                       const int32_t *sample_idx, uint64_t seed, const float *rot,
-                                       const int32_t *row_rot, float *obj_fts, float *obj_locs, float *obj_boxes,
-                                       uint8_t *obj_masks, gps_stream_t stream) {
+// One body for the by-value entry (seed_dev NULL) and the seed-word entry.
+static int obj_processing_post_launch(int n_rows, int n_points, const float *xyz, const void *rgb, int rgb_is_u8,
+                                      const int64_t *obj_offsets, const int32_t *row_obj, const int32_t *sample_idx,
+                                      uint64_t seed, const uint64_t *seed_dev, const float *rot, const int32_t *row_rot,
+                                      float *obj_fts, float *obj_locs, float *obj_boxes, uint8_t *obj_masks,
+                                      gps_stream_t stream) {
   if (n_rows < 0 || n_points <= 0) return GPS_ERR_INVALID_ARGUMENT;
   if (n_points > gps_obj::kBlock * gps_obj::kMaxPer) return GPS_ERR_UNSUPPORTED;
   if (n_rows == 0) return GPS_OK;
@@ -275,14 +283,32 @@ extern "C" int gps_obj_processing_post(int n_rows, int n_points, const float *xy
     if (((uintptr_t)xyz & 15u) != 0) return GPS_ERR_INVALID_ARGUMENT;
     hipLaunchKernelGGL(gps_obj::obj_processing_post_kernel<true>, dim3(n_rows), dim3(gps_obj::kBlock), 0,
                        (hipStream_t)stream, n_points, xyz, nullptr, nullptr, obj_offsets, row_obj, sample_idx, seed,
-                       rot, row_rot, obj_fts, obj_locs, obj_boxes, obj_masks);
+                       seed_dev, rot, row_rot, obj_fts, obj_locs, obj_boxes, obj_masks);
   } else {
     hipLaunchKernelGGL(gps_obj::obj_processing_post_kernel<false>, dim3(n_rows), dim3(gps_obj::kBlock), 0,
                        (hipStream_t)stream, n_points, xyz, rgb_is_u8 ? (const uint8_t *)rgb : nullptr,
-                       rgb_is_u8 ? nullptr : (const float *)rgb, obj_offsets, row_obj, sample_idx, seed, rot,
+                       rgb_is_u8 ? nullptr : (const float *)rgb, obj_offsets, row_obj, sample_idx, seed, seed_dev, rot,
                        row_rot, obj_fts, obj_locs, obj_boxes, obj_masks);
   }
   return hipGetLastError() == hipSuccess ? GPS_OK : GPS_ERR_LAUNCH;
+}
+
+extern "C" int gps_obj_processing_post(int n_rows, int n_points, const float *xyz, const void *rgb, int rgb_is_u8,
+                                       const int64_t *obj_offsets, const int32_t *row_obj,
+                                       const int32_t *sample_idx, uint64_t seed, const float *rot,
+                                       const int32_t *row_rot, float *obj_fts, float *obj_locs, float *obj_boxes,
+                                       uint8_t *obj_masks, gps_stream_t stream) {
+  return obj_processing_post_launch(n_rows, n_points, xyz, rgb, rgb_is_u8, obj_offsets, row_obj, sample_idx, seed,
+                                    nullptr, rot, row_rot, obj_fts, obj_locs, obj_boxes, obj_masks, stream);
+}
+
+extern "C" int gps_obj_processing_post_sw(int n_rows, int n_points, const float *xyz, const void *rgb, int rgb_is_u8,
+                                          const int64_t *obj_offsets, const int32_t *row_obj,
+                                          const int32_t *sample_idx, uint64_t seed, const uint64_t *seed_dev,
+                                          const float *rot, const int32_t *row_rot, float *obj_fts, float *obj_locs,
+                                          float *obj_boxes, uint8_t *obj_masks, gps_stream_t stream) {
+  return obj_processing_post_launch(n_rows, n_points, xyz, rgb, rgb_is_u8, obj_offsets, row_obj, sample_idx, seed,
+                                    seed_dev, rot, row_rot, obj_fts, obj_locs, obj_boxes, obj_masks, stream);
 }
 
 // ---- the augmented path ------------------------------------------------------------------------------
@@ -355,7 +381,8 @@ __global__ __launch_bounds__(kBlock) void obj_processing_aug_kernel(
     const float *__restrict__ rgb_f32, const int64_t *__restrict__ obj_offsets,
     const int32_t *__restrict__ row_obj, const int32_t *__restrict__ sample_idx,
     const float *__restrict__ noise_f32, const double *__restrict__ noise_f64, uint64_t seed,
-    const double *__restrict__ aug, const int32_t *__restrict__ row_aug, int n_aug, float *__restrict__ obj_fts,
+    const uint64_t *__restrict__ seed_dev, const double *__restrict__ aug, const int32_t *__restrict__ row_aug, int n_aug,
+    float *__restrict__ obj_fts,
     float *__restrict__ obj_locs, float *__restrict__ obj_boxes, uint8_t *__restrict__ obj_masks) {
   __shared__ double s_red[kWaves][9];
   __shared__ double s_out[9];
@@ -410,7 +437,7 @@ __global__ __launch_bounds__(kBlock) void obj_processing_aug_kernel(
 
   // ---- the sampled points, held in registers: flip, scale, jitter -> size ---------------------
   const bool replace = k < (uint32_t)n_points;
-  const uint64_t key = mix64(seed ^ mix64((uint64_t)row));   // per output row: a scene drawn twice differs
+  const uint64_t key = mix64(row_seed(seed, seed_dev) ^ mix64((uint64_t)row));   // per output row: a scene drawn twice differs
   const uint64_t nkey = mix64(key ^ 0x6A09E667F3BCC909ull);  // the jitter stream, independent of the sampler's
   double px[kMaxPer], py[kMaxPer], pz[kMaxPer];
   uint32_t src[kMaxPer];                         // sampled index, or (REC16) the record's colour word
@@ -532,12 +559,11 @@ __global__ __launch_bounds__(kBlock) void obj_processing_aug_kernel(
 
 }  // namespace gps_obj
 
-extern "C" int gps_obj_processing_aug(int n_rows, int n_points, const float *xyz, const void *rgb, int rgb_is_u8,
-                                      const int64_t *obj_offsets, const int32_t *row_obj,
-                                      const int32_t *sample_idx, const void *jitter_noise, int noise_is_f64,
-                                      uint64_t seed, const double *aug, const int32_t *row_aug, int n_aug,
-                                      float *obj_fts, float *obj_locs, float *obj_boxes, uint8_t *obj_masks,
-                                      gps_stream_t stream) {
+static int obj_processing_aug_launch(int n_rows, int n_points, const float *xyz, const void *rgb, int rgb_is_u8,
+                                     const int64_t *obj_offsets, const int32_t *row_obj, const int32_t *sample_idx,
+                                     const void *jitter_noise, int noise_is_f64, uint64_t seed, const uint64_t *seed_dev,
+                                     const double *aug, const int32_t *row_aug, int n_aug, float *obj_fts,
+                                     float *obj_locs, float *obj_boxes, uint8_t *obj_masks, gps_stream_t stream) {
   if (n_rows < 0 || n_points <= 0) return GPS_ERR_INVALID_ARGUMENT;
   if (n_points > gps_obj::kBlock * gps_obj::kMaxPer) return GPS_ERR_UNSUPPORTED;
   if (n_rows == 0) return GPS_OK;
@@ -550,12 +576,34 @@ extern "C" int gps_obj_processing_aug(int n_rows, int n_points, const float *xyz
     if (((uintptr_t)xyz & 15u) != 0) return GPS_ERR_INVALID_ARGUMENT;
     hipLaunchKernelGGL(gps_obj::obj_processing_aug_kernel<true>, dim3(n_rows), dim3(gps_obj::kBlock), 0,
                        (hipStream_t)stream, n_points, xyz, nullptr, nullptr, obj_offsets, row_obj, sample_idx, n32, n64,
-                       seed, aug, row_aug, n_aug, obj_fts, obj_locs, obj_boxes, obj_masks);
+                       seed, seed_dev, aug, row_aug, n_aug, obj_fts, obj_locs, obj_boxes, obj_masks);
   } else {
     hipLaunchKernelGGL(gps_obj::obj_processing_aug_kernel<false>, dim3(n_rows), dim3(gps_obj::kBlock), 0,
                        (hipStream_t)stream, n_points, xyz, rgb_is_u8 ? (const uint8_t *)rgb : nullptr,
-                       rgb_is_u8 ? nullptr : (const float *)rgb, obj_offsets, row_obj, sample_idx, n32, n64, seed, aug,
-                       row_aug, n_aug, obj_fts, obj_locs, obj_boxes, obj_masks);
+                       rgb_is_u8 ? nullptr : (const float *)rgb, obj_offsets, row_obj, sample_idx, n32, n64, seed,
+                       seed_dev, aug, row_aug, n_aug, obj_fts, obj_locs, obj_boxes, obj_masks);
   }
   return hipGetLastError() == hipSuccess ? GPS_OK : GPS_ERR_LAUNCH;
+}
+
+extern "C" int gps_obj_processing_aug(int n_rows, int n_points, const float *xyz, const void *rgb, int rgb_is_u8,
+                                      const int64_t *obj_offsets, const int32_t *row_obj,
+                                      const int32_t *sample_idx, const void *jitter_noise, int noise_is_f64,
+                                      uint64_t seed, const double *aug, const int32_t *row_aug, int n_aug,
+                                      float *obj_fts, float *obj_locs, float *obj_boxes, uint8_t *obj_masks,
+                                      gps_stream_t stream) {
+  return obj_processing_aug_launch(n_rows, n_points, xyz, rgb, rgb_is_u8, obj_offsets, row_obj, sample_idx, jitter_noise,
+                                   noise_is_f64, seed, nullptr, aug, row_aug, n_aug, obj_fts, obj_locs, obj_boxes,
+                                   obj_masks, stream);
+}
+
+extern "C" int gps_obj_processing_aug_sw(int n_rows, int n_points, const float *xyz, const void *rgb, int rgb_is_u8,
+                                         const int64_t *obj_offsets, const int32_t *row_obj,
+                                         const int32_t *sample_idx, const void *jitter_noise, int noise_is_f64,
+                                         uint64_t seed, const uint64_t *seed_dev, const double *aug,
+                                         const int32_t *row_aug, int n_aug, float *obj_fts, float *obj_locs,
+                                         float *obj_boxes, uint8_t *obj_masks, gps_stream_t stream) {
+  return obj_processing_aug_launch(n_rows, n_points, xyz, rgb, rgb_is_u8, obj_offsets, row_obj, sample_idx, jitter_noise,
+                                   noise_is_f64, seed, seed_dev, aug, row_aug, n_aug, obj_fts, obj_locs, obj_boxes,
+                                   obj_masks, stream);
 }

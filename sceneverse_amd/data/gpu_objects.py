@@ -22,6 +22,7 @@ the CPU path; oracle/obj_processing.py restates it for the tests).
 """
 from __future__ import annotations
 
+import ctypes
 import math
 from dataclasses import dataclass
 from typing import Dict, List, Mapping, Optional, Sequence
@@ -29,6 +30,7 @@ from typing import Dict, List, Mapping, Optional, Sequence
 import numpy as np
 import torch
 
+from .. import _native
 from .._launch import launch
 from ._resident import as_bool, need_finalized, need_gpu, outputs, seed_word, u64
 
@@ -355,14 +357,18 @@ def _scan_proposals(packed: PackedScans, scan_id) -> range:
 
 def obj_processing_post(packed: PackedScans, row_obj: torch.Tensor, num_points: int = 1024,
                         rot: Optional[torch.Tensor] = None, sample_idx: Optional[torch.Tensor] = None,
-                        seed: int = 0, need_boxes: bool = False, out: Optional[dict] = None) -> dict:
+                        seed: int = 0, need_boxes: bool = False, out: Optional[dict] = None,
+                        seed_dev: Optional[torch.Tensor] = None) -> dict:
     """row_obj (B, O) int32 object ids (-1 = padding) -> dict with obj_fts (B,O,num_points,6) f32,
     obj_locs (B,O,6) f32, obj_masks (B,O) bool [, obj_boxes (B,O,6) f32].
 
     rot: per-scene rotations (build_rotate_mat's matrix): a (B,3,3) tensor/array, or a length-B list
-    with None for the scenes it left unrotated; None = no rotation at all.
+    with None for the scenes it left unrotated; None = no rotation at all.  A ready pair (mats (n,3,3) f32,
+    row_rot (B*O,) int32) of tensors on the scans' device -- `draw_rot_table`'s -- is passed through untouched.
     sample_idx: (B,O,num_points) int32 object-local indices (np.random.choice draws, for bit-compatible
     replays of the reference loader) or None = drawn on the device from `seed`.
+    seed_dev: one int64 word on the scans' device: the samples are drawn from seed + *seed_dev, read on the device, so
+    a captured launch redraws when the word is advanced between replays (gps_obj_processing_post_sw); None = `seed`.
     out: optional {"obj_fts", "obj_locs", "obj_masks"} of preallocated contiguous tensors of those shapes (obj_masks bool
     or uint8) the kernel writes IN PLACE -- the static input buffers of a captured training step
     (`GPSTrainStep.static_inputs()`), so that no per-step copy of the 126 MB of object points is needed."""
@@ -373,12 +379,27 @@ def obj_processing_post(packed: PackedScans, row_obj: torch.Tensor, num_points: 
     row_obj, sample_idx, res = _obj_buffers("obj_processing_post", row_obj, num_points, sample_idx, need_boxes, out, dev)
     rot_t = row_rot = None
     if rot is not None:
-        rot_t, row_rot = rot_rows(rot, B, O, dev)
-    launch("gps_obj_processing_post", n_rows, num_points, packed.xyz, packed.rgb,
+        rot_t, row_rot = _rot_pair(rot, n_rows, dev) or rot_rows(rot, B, O, dev)
+    seed_word("obj_processing_post", seed_dev, dev, "scans")
+    word = () if seed_dev is None else (seed_dev,)
+    launch("gps_obj_processing_post" + ("_sw" if word else ""), n_rows, num_points, packed.xyz, packed.rgb,
            int(packed.rgb is None or packed.rgb.dtype == torch.uint8), packed.obj_offsets, row_obj, sample_idx,
-           u64(seed), rot_t, row_rot, res["obj_fts"], res["obj_locs"], res.get("obj_boxes"), res["obj_masks"], device=dev,
+           u64(seed), *word, rot_t, row_rot, res["obj_fts"], res["obj_locs"], res.get("obj_boxes"), res["obj_masks"], device=dev,
            label=f"obj_processing_post(rows={n_rows},P={num_points})", nbytes=nbytes, what="obj_processing_post")
     return as_bool(res, ("obj_masks",))
+
+
+def _rot_pair(rot, n_rows: int, dev):
+    """`rot` when it is a ready (mats (n,3,3) f32, row_rot (B*O,) int32) pair of device tensors, else None."""
+    if not (isinstance(rot, tuple) and len(rot) == 2 and all(torch.is_tensor(t) for t in rot)):
+        return None
+    mats, row_rot = rot
+    if (mats.dim() != 3 or tuple(mats.shape[1:]) != (3, 3) or mats.dtype != torch.float32 or row_rot.dtype != torch.int32
+            or tuple(row_rot.shape) != (n_rows,) or mats.device != dev or row_rot.device != dev
+            or not mats.is_contiguous() or not row_rot.is_contiguous()):
+        raise ValueError(f"obj_processing_post: a rotation pair is (mats (n,3,3) float32, row_rot ({n_rows},) int32), "
+                         "contiguous, on the scans' GPU")
+    return mats, row_rot
 
 
 def _obj_device(packed: PackedScans, what: str) -> torch.device:
@@ -593,7 +614,7 @@ class AugTable:
 def obj_processing_aug(packed: PackedScans, row_obj: torch.Tensor, num_points: int = 1024,
                        aug: "Optional[AugParams | AugTable]" = None, sample_idx: Optional[torch.Tensor] = None,
                        jitter_noise: Optional[torch.Tensor] = None, seed: int = 0, need_boxes: bool = False,
-                       out: Optional[dict] = None) -> dict:
+                       out: Optional[dict] = None, seed_dev: Optional[torch.Tensor] = None) -> dict:
     """ScanBase._obj_processing_aug (base.py:742-776) after DataAugmentor.update_data_dict (data_augmentor.py:156-215)
     for a whole batch in one launch; same return dict and the same in-place `out=` contract as obj_processing_post
     (so it fills `GPSTrainStep.static_inputs()` just the same).
@@ -603,7 +624,9 @@ def obj_processing_aug(packed: PackedScans, row_obj: torch.Tensor, num_points: i
     max_dist clamped at 1e-6).
     sample_idx (B,O,num_points) int32 / jitter_noise (B,O,num_points,3) float32 or float64: the reference's
     np.random.choice / np.random.randn draws for a replay -- already in the order the point shuffle left them; None =
-    drawn on the device from `seed` (the noise only for scenes whose obj_jitter is set)."""
+    drawn on the device from `seed` (the noise only for scenes whose obj_jitter is set).
+    seed_dev: one int64 word on the scans' device, as in obj_processing_post: samples and noise are drawn from
+    seed + *seed_dev (gps_obj_processing_aug_sw); None = `seed`."""
     dev = _obj_device(packed, "obj_processing_aug")
     B, O = row_obj.shape
     n_rows = B * O
@@ -622,9 +645,11 @@ def obj_processing_aug(packed: PackedScans, row_obj: torch.Tensor, num_points: i
             raise ValueError("obj_processing_aug: jitter_noise must be float32 or float64")
         jitter_noise = jitter_noise.to(device=dev).contiguous()
         assert jitter_noise.shape == (B, O, num_points, 3), jitter_noise.shape
-    launch("gps_obj_processing_aug", n_rows, num_points, packed.xyz, packed.rgb,
+    seed_word("obj_processing_aug", seed_dev, dev, "scans")
+    word = () if seed_dev is None else (seed_dev,)
+    launch("gps_obj_processing_aug" + ("_sw" if word else ""), n_rows, num_points, packed.xyz, packed.rgb,
            int(packed.rgb is None or packed.rgb.dtype == torch.uint8), packed.obj_offsets, row_obj, sample_idx, jitter_noise,
-           int(jitter_noise is not None and jitter_noise.dtype == torch.float64), u64(seed),
+           int(jitter_noise is not None and jitter_noise.dtype == torch.float64), u64(seed), *word,
            tab, row_aug, tab.shape[0] if tab is not None else 0, res["obj_fts"], res["obj_locs"], res.get("obj_boxes"),
            res["obj_masks"], device=dev, label=f"obj_processing_aug(rows={n_rows},P={num_points})", nbytes=nbytes,
            what="obj_processing_aug")
@@ -726,6 +751,107 @@ def draw_aug_params(aug_cfg, split: str, B: int, O: int, rng: np.random.Generato
         else:
             raise ValueError(f"draw_aug_params: unknown augmentor {name!r} in aug_list")
     return a
+
+
+def _knob(key, n_values: int = 3):
+    """One knob of the `data_aug:` schema as the plain numbers of struct gps_aug_knob: enabled by `_check_key`, p = 1.0
+    where the config gives none (check_p always fires then), the first n_values of `value`."""
+    k = _native.AugKnob()
+    k.enabled = int(_check_key(key))
+    k.p = 1.0
+    if k.enabled and isinstance(key, Mapping):
+        k.p = float(key.get("p", 1.0))
+        if not 0.0 <= k.p <= 1.0:
+            raise ValueError(f"draw_aug_table: p = {k.p} outside [0, 1]")
+        k.axis_align, k.shuffle = int(bool(key.get("axis_align", False))), int(bool(key.get("shuffle", False)))
+        for i in range(n_values):
+            k.value[i] = float(key["value"][i])
+    return k
+
+
+def aug_draw_args(aug_cfg, B: int, O: int, seed: int = 0, seed_dev: Optional[torch.Tensor] = None):
+    """The `data_aug:` block (any mapping) as struct gps_aug_draw_args -> (args, per_obj, has_scale): per_obj = some
+    per-object knob is on (the table then has B * O entries, else B), has_scale = the scaling knob is on."""
+    a = _native.AugDrawArgs()
+    a.mode, a.B, a.O, a.seed = _native.AUG_DRAW_TABLE, int(B), int(O), u64(seed)
+    a.seed_dev = None if seed_dev is None else seed_dev.data_ptr()
+    for name in aug_cfg["aug_list"]:
+        if name not in aug_cfg:
+            continue
+        cfg = aug_cfg[name]
+        if name == "scene_aug":
+            a.scene_on = 1
+            a.scene_trans, a.scene_scale = _knob(cfg.get("translation")), _knob(cfg.get("scaling"), 2)
+            a.scene_flip, a.scene_rot = _knob(cfg.get("flip"), 0), _knob(cfg.get("rotation"))
+            a.color_jitter = int(_check_key(cfg.get("color_jitter")))
+        elif name == "obj_aug":
+            a.obj_on = 1
+            a.obj_trans, a.obj_rot = _knob(cfg.get("translation")), _knob(cfg.get("rotation"))
+            a.jitter_on = int(_check_key(cfg.get("random_jitter")))
+            if a.jitter_on:
+                v = np.broadcast_to(np.asarray(cfg["random_jitter"]["value"], dtype=np.float64).reshape(-1), (3,))
+                a.jitter_value[0], a.jitter_value[1], a.jitter_value[2] = (float(x) for x in v)
+        else:
+            raise ValueError(f"draw_aug_table: unknown augmentor {name!r} in aug_list")
+    per_obj = bool(a.obj_on and (a.obj_trans.enabled or a.obj_rot.enabled))
+    return a, per_obj, bool(a.scene_on and a.scene_scale.enabled)
+
+
+def draw_aug_table(aug_cfg, split: str, B: int, O: int, seed: int = 0, seed_dev: Optional[torch.Tensor] = None,
+                   out: Optional[dict] = None, device=None) -> "Optional[AugTable]":
+    """`draw_aug_params` + `AugParams.to_device` as ONE launch (gps_aug_draw) and without a host loop, a host table or an
+    upload: the AugTable `obj_processing_aug` takes, drawn on the device from seed + *seed_dev by the law of
+    include/gps_hip.h (stream seed + 6; seed_dev: one int64 word on the device, advanced there between graph replays).
+    None -- nothing launched -- without a config and on a split other than 'train', like `draw_aug_params`.
+    The table's shape follows from the config alone: B entries, or B * O when a per-object knob is on; `has_scale` comes
+    from the config too.  out: optional {"entries" (n, AUG_STRIDE) float64, "row_aug" (B*O,) int32}, written IN PLACE.
+    device: where to draw, default the seed word's, else the current GPU.  The draws differ from `draw_aug_params`'
+    (another generator); that function stays the host and replay path."""
+    if aug_cfg is None or split != "train":
+        return None
+    args, per_obj, has_scale = aug_draw_args(aug_cfg, B, O, seed, seed_dev)
+    dev = _draw_device("draw_aug_table", seed_dev, out, device)
+    res = outputs("draw_aug_table", (("entries", torch.float64, (B * O if per_obj else B, AUG_STRIDE)),
+                                     ("row_aug", torch.int32, (B * O,))), out, dev, "scans")
+    launch("gps_aug_draw", ctypes.byref(args), res["entries"], res["row_aug"], None, None, device=dev,
+           label=f"aug_draw(B={B},O={O})", nbytes=res["entries"].numel() * 8 + 4 * B * O, what="draw_aug_table")
+    return AugTable(res["entries"], res["row_aug"], has_scale)
+
+
+def draw_rot_table(split: str, rot_aug: bool, B: int, O: int, seed: int = 0, seed_dev: Optional[torch.Tensor] = None,
+                   out: Optional[dict] = None, device=None):
+    """build_rotate_mat (data/data_utils.py:163-178, rand_angle 'axis') for a whole batch in one launch: the pair
+    (mats (B,3,3) f32, row_rot (B*O,) int32) `obj_processing_post(rot=...)` passes through, drawn on the device from
+    seed + *seed_dev (stream seed + 7 of include/gps_hip.h).  None -- nothing launched -- on a split other than 'train'
+    or with rot_aug off, where build_rotate_mat returns None for every scene.
+    out: optional {"rot" (B,3,3) float32, "row_rot" (B*O,) int32}, written IN PLACE."""
+    if split != "train" or not rot_aug:
+        return None
+    a = _native.AugDrawArgs()
+    a.mode, a.B, a.O, a.seed = _native.AUG_DRAW_ROT, int(B), int(O), u64(seed)
+    a.seed_dev = None if seed_dev is None else seed_dev.data_ptr()
+    dev = _draw_device("draw_rot_table", seed_dev, out, device)
+    res = outputs("draw_rot_table", (("rot", torch.float32, (B, 3, 3)), ("row_rot", torch.int32, (B * O,))), out, dev, "scans")
+    launch("gps_aug_draw", ctypes.byref(a), None, None, res["rot"], res["row_rot"], device=dev,
+           label=f"rot_draw(B={B},O={O})", nbytes=36 * B + 4 * B * O, what="draw_rot_table")
+    return res["rot"], res["row_rot"]
+
+
+def _draw_device(what: str, seed_dev, out, device) -> torch.device:
+    """Where a draw runs: `device`, else the seed word's, else the out buffers', else the current GPU."""
+    if device is not None:
+        dev = torch.device(device)
+        if dev.type == "cuda" and dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+    elif seed_dev is not None:
+        dev = seed_dev.device
+    elif out:
+        dev = next(iter(out.values())).device
+    else:
+        dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+    need_gpu(dev, what, "tables")
+    seed_word(what, seed_dev, dev, "tables")
+    return dev
 
 
 def rot_rows(rot, B: int, O: int, dev):
